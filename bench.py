@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X SpMV path.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python bench.py --workload queen|kkt|webbase|powerlaw [--format csr|coo|ell|hybrid]
     python bench.py --matrix Queen_4147.tar.gz [--expand-symmetric] [--format ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -18,7 +18,10 @@ With N > 1 GPUs the SAME matrix is row-partitioned (ceil(rows/N) rows per rank, 
 static chunk rule), x is replicated, and every step ends with ONE all-gather of the y segments
 (RCCL): total work is fixed, so scaling is "strong".
 
-Prints ONE JSON line on rank 0.  `value` = 2*Z*K / t in GFLOP/s (whole job).
+Prints ONE JSON line on rank 0.  `value` = 2*Z*K / t in GFLOP/s (whole job); `ms_per_step` = t / K, K = --steps.
+--dump-outputs DIR writes y as the K timed steps left it (warm-up + K multiplies accumulated from y = 0) to DIR/y.npy,
+float64; beyond 64 MB a fixed seeded sample of rows, their numbers in DIR/y_rows.npy.  Inputs are seeded: the same
+arguments give the same inputs on every run, so two builds can be compared output for output.
 
 The timed launch READS THE VALUE ARRAY (plan flag SPMV_HIP_FLAG_NO_VALUE_INDEX: what the kernel does for a matrix of this
 structure with arbitrary values), and `roofline` follows SURVEY section 8(d) to the letter: `achieved` = ALGORITHMIC bytes
@@ -197,7 +200,37 @@ def parse_args():
     ap.add_argument("--drop-in-specs", default="", help=argparse.SUPPRESS)            # internal: name=spec;name=spec
     ap.add_argument("--force-collective", action="store_true",
                     help="initialise the process group and run the all-gather even with one rank (rehearsal)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write y as the last timed step left it to DIR/<name>.npy (float64; a fixed seeded sample of rows "
+                         "where the whole vector passes %d MB)" % (DUMP_LIMIT_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # everything --dump-outputs writes, all files together
+DUMP_SAMPLE_SEED = 20240531
+
+
+def dump_outputs(dirname, y):
+    """--dump-outputs: y (what a caller of the timed path receives) as DIR/y.npy.  A vector larger than the budget is
+    written as a sample: rows drawn once with a fixed seed (the same rows for the same --grid / --matrix), sorted, their
+    values in y.npy and their indices in y_rows.npy (float64, exact below 2^53)."""
+    os.makedirs(dirname, exist_ok=True)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    files = {}
+    if y.nbytes <= DUMP_LIMIT_BYTES - 4096:
+        files["y"] = y
+    else:
+        n = (DUMP_LIMIT_BYTES - 4096) // 16  # values and row indices, 8 bytes each
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(y.size, size=n, replace=False))
+        files["y"] = y[rows]
+        files["y_rows"] = rows.astype(np.float64)
+    for name, arr in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    return {"dir": dirname, "files": {k: int(v.size) for k, v in files.items()}, "rows": int(y.size),
+            "sampled": "y_rows" in files}
 
 
 QUEEN_STORED_NAME = "queen-like 110x71x177 mesh x 3 dof, stored lower triangle (Queen_4147.mtx as the reference multiplies it)"
@@ -1334,6 +1367,15 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    # --dump-outputs: y as the last timed step left it (warm-up + K accumulated multiplies), taken before anything below
+    # multiplies into the same vector.  With a gather, op.y() waits for it and meets the other ranks: every rank calls it;
+    # without one, the rank's segment is the whole vector
+    dumped = None
+    if args.dump_outputs:
+        y_out = op.y() if (fmt != "csr" or use_dist) else op.y_local[:local_rows]
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, y_out if fmt != "csr" else y_out.cpu().numpy())
+        del y_out
     if per_launch:
         kernel_ms = np.array([a.elapsed_time(b) for a, b in zip(ev0, ev1)])
     else:
@@ -1813,6 +1855,8 @@ def main():
             if not gather_check["pass"]:
                 code, message = 1, "bench.py: gathered y does not match the owning rank's rows"
         out["build"] = build
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         tr = pmc_traffic(kernel_name, wname, int(local_bytes), out["roofline"].get("streamed_bytes_per_launch"), build, kern_s * 1e6)
         live = None
         under_profiler = any("ROCPROF" in k or k.startswith("ROCP_") for k in os.environ)  # (this run is itself a rocprofv3 child: no nesting)

@@ -61,6 +61,71 @@ def test_drop_in_child_without_a_device_says_so():
     assert d["devices_visible"] == 0 and d["devices"] == 2 and "2 devices asked for, 0 visible" in d["error"] and d["workloads"] == {}
 
 
+def _dump(y, out_dir):
+    """bench.dump_outputs in a process of its own (importing bench.py sets environment variables for the ranks)."""
+    code = ("import sys, json, numpy as np; sys.path.insert(0, %r); import bench; "
+            "print(json.dumps(bench.dump_outputs(%r, np.load(%r))))" % (ROOT, str(out_dir), str(y)))
+    r = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=_env(), timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_dump_outputs_whole_vector_and_seeded_sample(tmp_path):
+    """--dump-outputs writes y whole while it fits in 64 MB, else a sample of rows drawn with a fixed seed: the same rows on
+    every run, the values as float64 beside their row numbers, all files together within 64 MB."""
+    import numpy as np
+    small = np.random.default_rng(1).uniform(-1, 1, size=1000)
+    np.save(tmp_path / "small.npy", small)
+    d = _dump(tmp_path / "small.npy", tmp_path / "a")
+    assert d["sampled"] is False and sorted(os.listdir(tmp_path / "a")) == ["y.npy"]
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+
+    big = np.arange(9 << 20, dtype=np.float64) * 0.5  # 72 MB
+    np.save(tmp_path / "big.npy", big)
+    for name in ("b", "c"):
+        d = _dump(tmp_path / "big.npy", tmp_path / name)
+        assert d["sampled"] is True and d["rows"] == big.size
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= 64 << 20
+    y, rows = np.load(tmp_path / "b" / "y.npy"), np.load(tmp_path / "b" / "y_rows.npy")
+    assert y.dtype == np.float64 and rows.dtype == np.float64 and y.size == rows.size > 0
+    assert np.all(np.diff(rows) > 0) and np.array_equal(y, big[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "y_rows.npy")) and np.array_equal(y, np.load(tmp_path / "c" / "y.npy"))
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       env=_env(), timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_gpu_dump_outputs_is_y_of_the_timed_steps(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR` leaves y as the timed path left it: warm-up + K multiplies accumulated from y = 0, so
+    (W + K) A x up to rounding; `steps` in the line is the K asked for, and two runs with the same arguments dump the same bits."""
+    import numpy as np
+    from spmv_amd import hostapi, synth
+    W, K = 3, 7
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--grid", "256", "--steps", str(K), "--warmup", str(W), "--no-companions",
+           "--no-cpu-baseline", "--no-reference-protocol", "--no-live-pmc", "--no-drop-in", "--no-host-boundary", "--no-cold"]
+    ys = []
+    for name in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / name)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           env=_env(), timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == K and d["warmup"] == W and d["ms_per_step"] > 0
+        assert d["dumped_outputs"]["sampled"] is False and os.listdir(tmp_path / name) == ["y.npy"]
+        ys.append(np.load(tmp_path / name / "y.npy"))
+    assert np.array_equal(ys[0], ys[1])
+    A = hostapi.load("synthetic:poisson2d:256", "csr")
+    x = synth.x_vector(A.cols, "uniform", seed=12345)
+    want = oracle.csr_spmv(A.rows, A.row_ptr, A.column_index, A.value, x) * float(W + K)
+    A.close()
+    assert ys[0].dtype == np.float64 and ys[0].shape == want.shape
+    assert np.max(np.abs(ys[0] - want)) <= 1e-10 * np.max(np.abs(want))
+
+
 @pytest.mark.gpu
 def test_gpu_drop_in_child_one_device_and_shared_rehearsal():
     """The child by itself on this box's one device: G = 1 (one context, no gather: the launch bench.py times, through the
