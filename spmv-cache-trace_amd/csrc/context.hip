@@ -17,6 +17,10 @@ void free_ctx_matrix(spmv_hip_ctx * c)
         spmv_hip_plan_destroy(c->plan);
         c->plan = nullptr;
     }
+    if (c->sym_plan) {
+        spmv_hip_sym_plan_destroy(c->sym_plan);
+        c->sym_plan = nullptr;
+    }
     if (c->y_borrowed)
         c->d_y = nullptr;
     void * ptrs[] = {c->d_ptr, c->d_idx, c->d_col, c->d_col2, c->d_val, c->d_val2, c->d_x, c->d_y, c->d_prow, c->d_pcol, c->d_pval};
@@ -726,6 +730,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
     };
     switch (c->format) {
     case 1: rc = csr_run(); break;
+    case 5: rc = spmv_hip_csr_symv(c->sym_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
     case 2:
         rc = c->as_csr ? csr_run() : ctx_coo_run(c, c->nnz, c->d_idx, c->d_col, c->d_val);
         break;
@@ -856,6 +861,12 @@ int spmv_hip_ctx_info(spmv_hip_ctx * c, int64_t * out, int n)
         v[12] = c->plan->xwin_tiles;
         v[13] = c->plan->blockwin_tiles;
         v[14] = c->plan->inner ? c->plan->inner->ntiles : 0;
+    }
+    if (c->sym_plan) { // format 5: workgroups = ranges, streamed bytes of the stored triangle
+        int64_t si[14] = {0};
+        spmv_hip_sym_plan_info(c->sym_plan, si, 14);
+        v[6] = si[0];
+        v[15] = si[13];
     }
     if (c->d_prow)
         v[14] += c->coo_panel_blocks; // COO (part) in column panels: workgroups per panel

@@ -7,9 +7,11 @@
 //   multi_gpu.hip    one process, G devices: row blocks + one all-gather
 //   peer_gather.hip  one process per GPU: y segments stored straight into the other ranks' vectors
 //   coo_sort.hip     device sort of COO triplets, scans (hipCUB plumbing)
+//   symmetric.hip    the multiply of a stored triangle as the (skew-)symmetric matrix it stands for (spmv_hip_symmetric.h)
 #pragma once
 
 #include "spmv_hip_plan.h"
+#include "spmv_hip_symmetric.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -179,11 +181,12 @@ struct spmv_hip_ctx {
     hipStream_t own_stream = nullptr; // the stream spmv_hip_create made (destroyed with the context)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    int format = 0; // 0 none, 1 csr, 2 coo, 3 ell, 4 hybrid (ell + coo remainder)
+    int format = 0; // 0 none, 1 csr, 2 coo, 3 ell, 4 hybrid (ell + coo remainder), 5 stored triangle of a (skew-)symmetric matrix
     int32_t rows = 0, cols = 0, nnz = 0, row_length = 0, nnz2 = 0;
     int csr_algorithm = SPMV_HIP_CSR_AUTO;
     int csr_lanes = 0;
     spmv_hip_plan * plan = nullptr;
+    spmv_hip_sym_plan * sym_plan = nullptr; // format 5 (symmetric.hip)
     int32_t *d_ptr = nullptr, *d_idx = nullptr, *d_col = nullptr, *d_col2 = nullptr;
     double *d_val = nullptr, *d_val2 = nullptr, *d_x = nullptr, *d_y = nullptr;
     size_t bytes = 0;

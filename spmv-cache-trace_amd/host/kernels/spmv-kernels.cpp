@@ -5,6 +5,7 @@
 #include "../matrix/matrix-reorder.hpp"
 #include "../matrix/synthetic.hpp"
 
+#include "spmv_hip_symmetric.h" // (spmv_hip_plan.h, spmv_hip_tuning.h, spmv_hip.h)
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -450,6 +451,67 @@ private:
     csr_matrix::Matrix A;
 };
 
+// --symmetric: the stored triangle T of a `symmetric` / `skew-symmetric` file (or a synthetic:...:tril spec) stays as it is on the
+// device and every run adds (T + T' - diag(T)) x, or (T - T') x, to y: the product of the matrix the file stands for, from half
+// the values (the reference multiplies T alone; --expand-symmetric mirrors it on the host instead)
+class hip_csr_symmetric_spmv_kernel : public hip_kernel_base
+{
+public:
+    using hip_kernel_base::hip_kernel_base;
+    void init(TraceConfig const &, std::ostream & o, bool verbose) override
+    {
+        auto const t0 = std::chrono::steady_clock::now();
+        guarded_init(matrix_path, [&] {
+            if (synthetic::is_spec(matrix_path) && synthetic::is_stored_triangle(matrix_path)) {
+                A = load_csr(matrix_path, options, o, verbose);
+                kind = SPMV_HIP_SYMMETRIC;
+            } else {
+                matrix_market::Matrix mm = matrix_market::load_matrix(matrix_path, o, verbose);
+                switch (mm.symmetry()) {
+                case matrix_market::Symmetry::symmetric: kind = SPMV_HIP_SYMMETRIC; break;
+                case matrix_market::Symmetry::skew_symmetric: kind = SPMV_HIP_SKEW_SYMMETRIC; break;
+                case matrix_market::Symmetry::hermitian: throw matrix::matrix_error("--symmetric: hermitian files are not supported");
+                default: throw matrix::matrix_error("--symmetric needs a file with a `symmetric` or `skew-symmetric` header; this one is general");
+                }
+                A = csr_matrix::from_matrix_market(mm);
+            }
+            if (A.rows != A.columns)
+                throw matrix::matrix_error("--symmetric needs a square matrix");
+            x.assign((std::size_t) A.columns, 1.0);
+            y.assign((std::size_t) A.rows, 0.0);
+        });
+        std::int64_t diag = 0;
+        check(spmv_hip_csr_triangle(A.rows, A.row_ptr.data(), A.column_index.data(), &triangle, &diag), "csr_triangle");
+        diagonal = diag;
+        auto const t1 = std::chrono::steady_clock::now();
+        create_context();
+        check(spmv_hip_upload_csr_symmetric(ctx, A.rows, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(), A.column_index.data(),
+                                            A.value.data(), kind), "upload_csr_symmetric");
+        init_load_seconds = std::chrono::duration<double>(t1 - t0).count();
+        init_upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    }
+    std::string name() const override { return "hip-csr-spmv-symmetric"; }
+    std::ostream & print(std::ostream & o) const override
+    {
+        static char const * const triangles[] = {"mixed", "lower", "upper", "diagonal"};
+        print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
+        o << ",\n\"symmetry\": \"" << (kind == SPMV_HIP_SKEW_SYMMETRIC ? "skew-symmetric" : "symmetric") << "\""
+          << ",\n\"stored_triangle\": \"" << triangles[triangle >= 0 && triangle <= 3 ? triangle : 0] << "\""
+          << ",\n\"multiplied_entries\": " << multiplied();
+        return print_device(o) << "\n}";
+    }
+
+    double flops_per_run() const override { return 2.0 * (double) multiplied(); }
+    double bytes_per_run() const override { return 12.0 * A.row_ptr[(std::size_t) A.rows] + 4.0 * (A.rows + 1.0) + 16.0 * A.rows + 8.0 * A.columns; }
+
+private:
+    long long multiplied() const { return 2LL * A.row_ptr[(std::size_t) A.rows] - diagonal; }
+    csr_matrix::Matrix A;
+    int kind = SPMV_HIP_SYMMETRIC;
+    int triangle = SPMV_HIP_TRIANGLE_DIAGONAL;
+    long long diagonal = 0;
+};
+
 class hip_coo_spmv_kernel : public hip_kernel_base
 {
 public:
@@ -545,6 +607,7 @@ std::unique_ptr<Kernel> make_spmv_kernel(SpmvFormat format, bool hip, std::strin
 {
     switch (format) {
     case SpmvFormat::csr:
+        if (hip && opt.symmetric) return std::make_unique<hip_csr_symmetric_spmv_kernel>(path, opt);
         if (hip) return std::make_unique<hip_csr_spmv_kernel>(path, opt);
         return std::make_unique<csr_spmv_kernel>(path, opt);
     case SpmvFormat::coo:

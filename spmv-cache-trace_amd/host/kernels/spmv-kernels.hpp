@@ -6,6 +6,8 @@
 //   hip_csr_spmv_kernel / hip_coo_spmv_kernel / hip_ell_spmv_kernel
 //       the same three formats multiplied on an MI355X through the C ABI (include/spmv_hip.h).
 //       No fallback: if the device library cannot run, init() throws kernel_error.
+//   hip_csr_symmetric_spmv_kernel (--symmetric)
+//       the stored triangle of a symmetric / skew-symmetric file multiplied as the whole matrix, each stored value read once.
 //
 // All of them load the matrix in init() exactly as the reference does (Matrix Market file ->
 // format conversion, x = 1.0, y = 0.0, errors rewrapped as "<path>: <what>") and print the same
@@ -34,6 +36,8 @@ struct SpmvOptions
     int csr_algorithm = 0;         // SPMV_HIP_CSR_*
     int csr_lanes_per_row = 0;
     unsigned hip_flags = 0;        // SPMV_HIP_FLAG_*
+    bool symmetric = false;        // EXTENSION: multiply the stored triangle of a (skew-)symmetric file as the whole matrix
+                                   // (hip-csr only: spmv_hip_upload_csr_symmetric, include/spmv_hip_symmetric.h)
 };
 
 enum class SpmvFormat { csr, coo, coo_atomic, ell, hybrid };

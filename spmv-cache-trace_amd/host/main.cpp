@@ -9,6 +9,7 @@
 // counters are outside this engine and are refused with a message.
 #include "kernels/spmv-kernels.hpp"
 #include "kernels/triad-kernel.hpp"
+#include "matrix/synthetic.hpp"
 #include "matrix/matrix-market.hpp"
 #include "profile-kernel.hpp"
 #include "trace-config.hpp"
@@ -91,6 +92,7 @@ enum Key
     key_synthetic,
     key_x,
     key_gpus,
+    key_symmetric,
 };
 
 bool parse_count(char const * arg, long long & out)
@@ -195,9 +197,33 @@ error_t parse_option(int key, char * arg, argp_state * state)
         else if (!std::strcmp(arg, "uniform")) a.x_uniform = true;
         else argp_error(state, "x: expected 'ones' or 'uniform'");
         break;
+    case key_symmetric: a.spmv.symmetric = true; break;
     case ARGP_KEY_END:
         if (a.list_perf_events)
             break;
+        if (a.spmv.symmetric) {
+            // what --symmetric runs on: the stored triangle of a (skew-)symmetric matrix, hip-csr on one device; anything else is
+            // refused here rather than multiplied some other way
+            if (a.spmv.expand_symmetric)
+                argp_error(state, "--symmetric multiplies the stored triangle as the whole matrix: it cannot be combined with --expand-symmetric");
+            if (a.kernel_type != KernelType::spmv || a.format != SpmvFormat::csr)
+                argp_error(state, "--symmetric needs the CSR kernel on the GPU (--spmv-format hip-csr or --csr PATH): "
+                                  "there is no symmetric COO, ELLPACK or hybrid kernel");
+            if (!a.hip && (!a.shortcut || a.device_given))
+                argp_error(state, "--symmetric runs on the GPU only (--spmv-format hip-csr or --device hip): there is no CPU symmetric kernel");
+            if (a.spmv.num_gpus > 1)
+                argp_error(state, "--symmetric runs on one device: a row partition would send transposed products across devices (--gpus must be 1)");
+            if (synthetic::is_spec(a.matrix_path)) {
+                if (!synthetic::is_stored_triangle(a.matrix_path))
+                    argp_error(state, "--symmetric needs a stored triangle: a synthetic spec ending in :tril, or a file with a "
+                                      "`symmetric` or `skew-symmetric` header");
+            } else if (!a.matrix_path.empty()) {
+                std::string const w = matrix_market::banner_symmetry(a.matrix_path);
+                if (w == "general" || w == "hermitian")
+                    argp_error(state, "--symmetric needs a file with a `symmetric` or `skew-symmetric` header; %s is %s",
+                               a.matrix_path.c_str(), w.c_str());
+            }
+        }
         if (a.trace_config.empty() && a.threads == 0 && a.write_mtx.empty())
             argp_error(state, "Please specify --trace-config");
         break;
@@ -279,6 +305,10 @@ int main(int argc, char ** argv)
          "EXTENSION: the vector multiplied: all ones like the reference (default), or uniform(-1,1) hashes", 2},
         {"expand-symmetric", key_expand_symmetric, nullptr, 0,
          "EXTENSION: mirror the entries of symmetric files (the reference multiplies the stored triangle only)", 2},
+        {"symmetric", key_symmetric, nullptr, 0,
+         "EXTENSION (hip-csr, one device): multiply the stored triangle of a symmetric or skew-symmetric file (or a synthetic:...:tril "
+         "spec) as the whole matrix -- y += (T + T' - diag T) x, or (T - T') x -- reading every stored value once; --check then "
+         "compares with the CPU CSR kernel on the expanded matrix.  Partial sums meet in atomics: not bit-reproducible", 2},
         {"matrix-cache", key_matrix_cache, "DIR", 0,
          "EXTENSION: keep the parsed entries of every matrix file in DIR and read them back next time "
          "(keyed by path, size and modification time; also: environment SPMV_MATRIX_CACHE)", 2},
@@ -368,8 +398,14 @@ int main(int argc, char ** argv)
         int count = 0;
         if (spmv_hip_device_count(&count) == 0 && count > 0)
             args.hip = true;
-        else
+        else if (!args.spmv.symmetric) // (--symmetric fails below: nothing runs in its place)
             std::cerr << "note: no usable HIP device: the CPU (OpenMP) kernel runs (--device hip makes this an error, --device cpu silences the note)\n";
+    }
+
+    if (args.spmv.symmetric && !args.hip) {
+        std::cerr << "--symmetric: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU symmetric kernel "
+                     "(nothing runs in its place)\n";
+        return EXIT_FAILURE;
     }
 
     std::unique_ptr<Kernel> kernel;
@@ -410,14 +446,21 @@ int main(int argc, char ** argv)
         } else if (args.check && args.kernel_type == KernelType::spmv) {
             // the same matrix through the CPU CSR kernel, one thread, warm-up + N accumulating runs
             TraceConfig one = default_trace_config(1);
-            std::unique_ptr<Kernel> ref = make_spmv_kernel(SpmvFormat::csr, false, args.matrix_path, args.spmv);
+            // (--symmetric: the matrix expand_symmetry builds from the same file -- an independent path to the same product)
+            SpmvOptions ref_options = args.spmv;
+            if (args.spmv.symmetric) {
+                ref_options.symmetric = false;
+                ref_options.expand_symmetric = true;
+            }
+            std::unique_ptr<Kernel> ref = make_spmv_kernel(SpmvFormat::csr, false, args.matrix_path, ref_options);
             ref->init(one, std::cerr, false);
             if (!xv.empty())
                 ref->set_x(xv);
             for (int r = 0; r < args.profile + 1; ++r)
                 ref->run(one);
             double const err = relative_error(kernel->result(), ref->result());
-            parity = ",\n\"parity\": {\"against\": \"csr-spmv (CPU, 1 thread), " + std::to_string(args.profile + 1) +
+            parity = ",\n\"parity\": {\"against\": \"csr-spmv (CPU, 1 thread)" +
+                std::string(args.spmv.symmetric ? " on the expanded matrix (expand_symmetry)" : "") + ", " + std::to_string(args.profile + 1) +
                 " accumulating runs\", \"max_relative_error\": ";
             char buf[64];
             if (std::isnan(err))

@@ -769,6 +769,28 @@ Matrix sort_matrix_column_major(Matrix const & m)
                   permuted(m.a_, order), permuted(m.imag_, order));
 }
 
+// gzopen reads plain and gzip'ed files alike
+std::string banner_symmetry(std::string const & path)
+{
+    if (path.size() > 7 && (path.compare(path.size() - 7, 7, ".tar.gz") == 0 || path.compare(path.size() - 4, 4, ".tgz") == 0))
+        return "";
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f)
+        return "";
+    char line[1024] = {0};
+    char const * got = gzgets(f, line, sizeof line);
+    gzclose(f);
+    if (!got)
+        return "";
+    char banner[64] = {0}, object[64] = {0}, format[64] = {0}, field[64] = {0}, symmetry[64] = {0};
+    if (std::sscanf(line, "%63s %63s %63s %63s %63s", banner, object, format, field, symmetry) != 5 || std::strcmp(banner, "%%MatrixMarket"))
+        return "";
+    std::string w(symmetry);
+    for (char & ch : w)
+        ch = (char) std::tolower((unsigned char) ch);
+    return w;
+}
+
 Matrix expand_symmetry(Matrix const & m)
 {
     if (m.symmetry() == Symmetry::general || m.format() != Format::coordinate)

@@ -117,6 +117,10 @@ std::vector<size_type> row_major_order(Matrix const & m);
 Matrix sort_matrix_row_major(Matrix const & m);
 Matrix sort_matrix_column_major(Matrix const & m);
 
+// EXTENSION: the symmetry word of a Matrix Market file's banner ("general", "symmetric", ...), lower case, read from the first
+// line alone; "" if the file cannot be read, has no banner or is an archive (tar members are looked at when they are loaded).
+std::string banner_symmetry(std::string const & path);
+
 // EXTENSION (not in the reference, off by default): mirror the off-diagonal entries of a
 // symmetric / skew-symmetric / hermitian file so the full matrix is multiplied.
 Matrix expand_symmetry(Matrix const & m);

@@ -1,4 +1,4 @@
-"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h and spmv_hip_plan.h (the C ABI of libspmv_hip.so).
+"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h and spmv_hip_symmetric.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -17,9 +17,11 @@ if os.environ.get("SPMV_HIP_EXPERIMENTS") == "1":
     LIB_PATH = EXPERIMENTS_LIB_PATH
 elif os.environ.get("SPMV_HIP_EXPERIMENTS", "").endswith(".so"):  # an ablation build of tools/ablate.sh
     LIB_PATH = os.path.abspath(os.environ["SPMV_HIP_EXPERIMENTS"])
-# the drop-in boundary (what an adapter of the reference binds) and the two headers that include it (tuning switches; Level 2)
+# the drop-in boundary (what an adapter of the reference binds) and the headers that include it (tuning switches; Level 2;
+# the symmetric multiply of a stored triangle)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
-HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n) for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h")]
+HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
+                                for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -43,6 +45,10 @@ FLAG_NO_MULTI_WINDOW = 0x8000000
 FLAG_NO_MASKED_BLOCKS = 0x20000000
 FLAG_ROW_GROUPS = 0x10000000  # libspmv_hip_experiments.so only (retired from the product: csrc/internal.hpp)
 CSR_ALGORITHM_NAMES = {1: "scalar", 2: "vector", 3: "adaptive", 4: "wavetile"}
+# spmv_hip_symmetric.h
+SYMMETRIC, SKEW_SYMMETRIC = 1, 2
+TRIANGLE_MIXED, TRIANGLE_LOWER, TRIANGLE_UPPER, TRIANGLE_DIAGONAL = 0, 1, 2, 3
+TRIANGLE_NAMES = {0: "mixed", 1: "lower", 2: "upper", 3: "diagonal"}
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -96,6 +102,12 @@ SIGNATURES = {
     "spmv_hip_ell_to_column_major": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_ell_spmv": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_triad": (C.c_int, [C.c_int64, _vp, _vp, _vp, C.c_double, _vp]),
+    "spmv_hip_csr_triangle": (C.c_int, [C.c_int32, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "spmv_hip_upload_csr_symmetric": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
+    "spmv_hip_sym_plan_csr": (C.c_int, [C.POINTER(_vp), C.c_int32, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "spmv_hip_csr_symv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_sym_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
+    "spmv_hip_sym_plan_destroy": (None, [_vp]),
 }
 
 
@@ -252,6 +264,16 @@ class Context:
                                               coo_row, coo_col, coo_val))
         self.rows, self.cols = rows, cols
 
+    def upload_csr_symmetric(self, rows, row_ptr, col, val, kind=SYMMETRIC):
+        """The stored triangle (lower or upper, diagonal included) of a square (skew-)symmetric matrix: runs then add
+        (T + T' - diag(T)) x, or (T - T') x for kind=SKEW_SYMMETRIC, to y (include/spmv_hip_symmetric.h)."""
+        row_ptr, col, val = _i32(row_ptr), _i32(col), _f64(val)
+        nnz = int(row_ptr[rows]) if len(row_ptr) > rows else -1
+        if len(col) == 0:
+            col, val = _EMPTY_I32, _EMPTY_F64
+        check(self.lib.spmv_hip_upload_csr_symmetric(self.h, rows, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, kind))
+        self.rows, self.cols = rows, rows
+
     def set_x(self, x):
         x = _f64(x)
         assert len(x) == self.cols
@@ -363,6 +385,65 @@ class CsrPlan:
     def refresh_values(self, d_row_ptr, d_col, d_val, stream=0):
         """Re-copy the values into the plan's column-panel copy (no-op without panels)."""
         check(self.lib.spmv_hip_plan_csr_refresh_values(self.h, d_row_ptr, d_col, d_val, stream))
+
+
+def csr_triangle(rows, row_ptr, col):
+    """(triangle, diagonal entries) of a square CSR matrix: TRIANGLE_LOWER / _UPPER / _DIAGONAL (no off-diagonal entry) /
+    _MIXED.  Host only."""
+    row_ptr, col = _i32(row_ptr), _i32(col)
+    if len(row_ptr) < rows + 1:
+        raise ValueError("row_ptr needs rows + 1 entries")
+    if len(col) == 0:
+        col = _EMPTY_I32
+    t, d = C.c_int(-1), C.c_int64(-1)
+    check(load().spmv_hip_csr_triangle(rows, row_ptr.ctypes.data, col.ctypes.data, C.byref(t), C.byref(d)))
+    return t.value, d.value
+
+
+class SymPlan:
+    """Level-2 plan of the symmetric multiply of a stored triangle (spmv_hip_sym_plan_*): host row_ptr, device columns.
+    max_windows / window_doubles = 0: automatic (small values force spilled entries)."""
+
+    INFO_KEYS = ["ranges", "rows_per_range", "max_windows", "windows", "lds_bytes", "spilled_entries", "atomic_bytes",
+                 "stored_entries", "diagonal_entries", "triangle", "device_bytes", "kind", "rows", "streamed_bytes",
+                 "window_slots", "multiplied_entries"]
+
+    def __init__(self, rows, host_row_ptr, d_col, kind=SYMMETRIC, max_windows=0, window_doubles=0, stream=0):
+        self.lib = load()
+        self.h = None
+        rp = _i32(host_row_ptr)
+        if len(rp) < rows + 1:
+            raise ValueError("host_row_ptr needs rows + 1 entries")
+        h = _vp()
+        check(self.lib.spmv_hip_sym_plan_csr(C.byref(h), rows, rp.ctypes.data, d_col, kind, max_windows, window_doubles, stream))
+        self.h = h
+        self.rows = rows
+
+    def close(self):
+        if self.h:
+            self.lib.spmv_hip_sym_plan_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.int64)
+        check(self.lib.spmv_hip_sym_plan_info(self.h, out, len(out)))
+        return dict(zip(self.INFO_KEYS, out.tolist()))
+
+    def symv(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
+        """y += (T + T' - diag(T)) x (or (T - T') x); raw device addresses, d_x != d_y."""
+        check(self.lib.spmv_hip_csr_symv(self.h, d_row_ptr, d_col, d_val, d_x, d_y, stream))
 
 
 def ipc_alloc(nbytes):
