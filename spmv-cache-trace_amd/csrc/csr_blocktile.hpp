@@ -82,6 +82,11 @@ constexpr int kTileMetaGroupRows = 1 << 30; // only together with kTileMetaBlock
 // with 2 / 4 unknowns per node -- so x is read 16 bytes at a time, one gather per pair, and the group stream holds one column per pair:
 // 1 / D bytes per entry (the bit that marks masked 3 x 3 blocks otherwise)
 constexpr int kTileMetaGroupPairs = 1 << 29;
+// ... and, with kTileMetaGroupRows: a WIDE group tile (its group columns are 32-bit absolute ones in its own 16-bit slots, see
+// tile_products_grouped).  Not inferred from a missing kTileMetaNarrow: a plan that gives its segment windows up clears Narrow from
+// every tile they claimed (csr_clear_segwin_kernel), and a claimed narrow group tile keeps its 16-bit group stream.  (The bit of
+// balanced plans' tiles, kTileMetaSeg: balanced plans have no group tiles, and every kernel that marks or claims tiles rejects it.)
+constexpr int kTileMetaGroupWide = 1 << 21;
 // the group stream shares the block stream's place behind the 16-bit columns (a plan has 3 x 3 blocks or row groups, not both);
 // a tile's group entries start at k0 / D: every tile in front of it holds at most (its entries / D)
 __host__ __device__ __forceinline__ int group_stream_index(int k0, int d) { return k0 / d; }
@@ -635,7 +640,7 @@ static __global__ __launch_bounds__(256) void csr_group_mark_kernel(
         }
     }
     if (lane == 0) {
-        desc[w].z = meta | kTileMetaBlock3 | kTileMetaGroupRows | (adjacent ? kTileMetaGroupPairs : 0);
+        desc[w].z = meta | kTileMetaBlock3 | kTileMetaGroupRows | (adjacent ? kTileMetaGroupPairs : 0) | (wide ? kTileMetaGroupWide : 0);
         striped_add(count, 0, 1ull);
         striped_add(count, 1, (unsigned long long) n);
         if (!(meta & kTileMetaBlockWin)) {

@@ -847,7 +847,7 @@ __global__ __launch_bounds__(256, (TILE <= 512 ? 8 : 4)) void csr_wavetile_kerne
             // rows in groups of 2 or 4 with the same columns (csr_blocktile.hpp): one column list and one x per group; the row
             // sums below are the plain tile's
             // (a WIDE group tile -- no 16-bit columns -- keeps 32-bit absolute group columns in its own slots of the 16-bit stream)
-            const bool gwide = !(meta & kTileMetaNarrow);
+            const bool gwide = (meta & kTileMetaGroupWide) != 0;
             const uint16_t * gt = gwide ? j16 + wide_group_first_slot(k0) : j16 + block_stream_offset(nnz_total) + group_stream_index(k0, group_rows);
             const double * gx = gwide ? x : x + cbase;
             const unsigned glimit = (unsigned) (cols - 1 - (gwide ? 0 : cbase));
