@@ -21,6 +21,16 @@ void free_ctx_matrix(spmv_hip_ctx * c)
         spmv_hip_sym_plan_destroy(c->sym_plan);
         c->sym_plan = nullptr;
     }
+    if (c->mv_plan) {
+        spmv_hip_mv_plan_destroy(c->mv_plan);
+        c->mv_plan = nullptr;
+    }
+    if (c->d_bx) (void) hipFree(c->d_bx);
+    if (c->d_by) (void) hipFree(c->d_by);
+    c->d_bx = c->d_by = nullptr;
+    c->block_k = 0;
+    c->block_x_set = false;
+    c->block_bytes = 0;
     if (c->y_borrowed)
         c->d_y = nullptr;
     void * ptrs[] = {c->d_ptr, c->d_idx, c->d_col, c->d_col2, c->d_val, c->d_val2, c->d_x, c->d_y, c->d_prow, c->d_pcol, c->d_pval};

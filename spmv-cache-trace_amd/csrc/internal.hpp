@@ -8,10 +8,12 @@
 //   peer_gather.hip  one process per GPU: y segments stored straight into the other ranks' vectors
 //   coo_sort.hip     device sort of COO triplets, scans (hipCUB plumbing)
 //   symmetric.hip    the multiply of a stored triangle as the (skew-)symmetric matrix it stands for (spmv_hip_symmetric.h)
+//   multivec.hip     Y += A X for up to 16 vectors in one pass over a CSR matrix (spmv_hip_multivec.h)
 #pragma once
 
 #include "spmv_hip_plan.h"
 #include "spmv_hip_symmetric.h"
+#include "spmv_hip_multivec.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -187,6 +189,13 @@ struct spmv_hip_ctx {
     int csr_lanes = 0;
     spmv_hip_plan * plan = nullptr;
     spmv_hip_sym_plan * sym_plan = nullptr; // format 5 (symmetric.hip)
+    // block vectors of spmv_hip_run_block (multivec.hip; format 1 only): X (cols x block_k) and Y (rows x block_k), row-major,
+    // apart from d_x / d_y; the plan is made on the first run_block after the matrix or k changed
+    spmv_hip_mv_plan * mv_plan = nullptr;
+    double *d_bx = nullptr, *d_by = nullptr;
+    int block_k = 0;
+    bool block_x_set = false;
+    size_t block_bytes = 0;
     int32_t *d_ptr = nullptr, *d_idx = nullptr, *d_col = nullptr, *d_col2 = nullptr;
     double *d_val = nullptr, *d_val2 = nullptr, *d_x = nullptr, *d_y = nullptr;
     size_t bytes = 0;

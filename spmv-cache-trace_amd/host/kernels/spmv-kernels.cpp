@@ -6,6 +6,7 @@
 #include "../matrix/synthetic.hpp"
 
 #include "spmv_hip_symmetric.h" // (spmv_hip_plan.h, spmv_hip_tuning.h, spmv_hip.h)
+#include "spmv_hip_multivec.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -512,6 +513,87 @@ private:
     long long diagonal = 0;
 };
 
+// --vectors K: Y += A X for K vectors in one multiply (spmv_hip_run_block).  Column c of X is x * (c + 1), x being what the
+// single-vector kernel multiplies (ones, or --x uniform); result() is Y row-major, rows x K.
+class hip_csr_multivec_spmv_kernel : public hip_kernel_base
+{
+public:
+    using hip_kernel_base::hip_kernel_base;
+    void init(TraceConfig const &, std::ostream & o, bool verbose) override
+    {
+        auto const t0 = std::chrono::steady_clock::now();
+        guarded_init(matrix_path, [&] {
+            A = load_csr(matrix_path, options, o, verbose);
+            x.assign((std::size_t) A.columns, 1.0);
+            y.assign((std::size_t) A.rows, 0.0);
+        });
+        auto const t1 = std::chrono::steady_clock::now();
+        create_context();
+        check(spmv_hip_upload_csr(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(),
+                                  A.column_index.data(), A.value.data()), "upload_csr");
+        init_load_seconds = std::chrono::duration<double>(t1 - t0).count();
+        init_upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    }
+
+    void prepare(TraceConfig const &) override
+    {
+        if (is_master()) {
+            prepare_error.clear();
+            try {
+                int const k = options.vectors;
+                std::vector<double> X(x.size() * (std::size_t) k), Y(y.size() * (std::size_t) k, 0.0);
+                for (std::size_t i = 0; i < x.size(); ++i)
+                    for (int c = 0; c < k; ++c)
+                        X[i * (std::size_t) k + (std::size_t) c] = x[i] * (c + 1.0);
+                check(spmv_hip_set_block_x(ctx, k, X.data()), "set_block_x");
+                check(spmv_hip_set_block_y(ctx, k, Y.data()), "set_block_y");
+            } catch (kernel_error const & e) {
+                prepare_error = e.what();
+            }
+        }
+#pragma omp barrier
+        if (!prepare_error.empty())
+            throw kernel_error(prepare_error);
+    }
+
+    void run(TraceConfig const &) override
+    {
+        if (is_master()) {
+            check(spmv_hip_run_block(ctx), "run_block");
+            check(spmv_hip_sync(ctx), "sync");
+            std::uint64_t ns = 0;
+            if (spmv_hip_last_run_ns(ctx, &ns) == SPMV_HIP_OK)
+                device_ns = ns;
+        }
+    }
+
+    std::vector<double> result() const override
+    {
+        std::vector<double> out(y.size() * (std::size_t) options.vectors);
+        check(spmv_hip_get_block_y(ctx, options.vectors, out.empty() ? nullptr : out.data()), "get_block_y");
+        return out;
+    }
+
+    std::string name() const override { return "hip-csr-spmm"; }
+    std::ostream & print(std::ostream & o) const override
+    {
+        print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
+        o << ",\n\"vectors\": " << options.vectors;
+        return print_device(o) << "\n}";
+    }
+
+    // the matrix once, X once, Y read and written (one pass: k = 1, 2, 3, 4, 6, 8; the model of spmv_hip_mv_plan_info [6])
+    double flops_per_run() const override { return 2.0 * A.num_entries * options.vectors; }
+    double bytes_per_run() const override
+    {
+        double const k = options.vectors;
+        return 12.0 * A.row_ptr[(std::size_t) A.rows] + 4.0 * (A.rows + 1.0) + 16.0 * k * A.rows + 8.0 * k * A.columns;
+    }
+
+private:
+    csr_matrix::Matrix A;
+};
+
 class hip_coo_spmv_kernel : public hip_kernel_base
 {
 public:
@@ -608,6 +690,7 @@ std::unique_ptr<Kernel> make_spmv_kernel(SpmvFormat format, bool hip, std::strin
     switch (format) {
     case SpmvFormat::csr:
         if (hip && opt.symmetric) return std::make_unique<hip_csr_symmetric_spmv_kernel>(path, opt);
+        if (hip && opt.vectors > 0) return std::make_unique<hip_csr_multivec_spmv_kernel>(path, opt);
         if (hip) return std::make_unique<hip_csr_spmv_kernel>(path, opt);
         return std::make_unique<csr_spmv_kernel>(path, opt);
     case SpmvFormat::coo:

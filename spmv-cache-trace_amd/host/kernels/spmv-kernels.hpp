@@ -38,6 +38,7 @@ struct SpmvOptions
     unsigned hip_flags = 0;        // SPMV_HIP_FLAG_*
     bool symmetric = false;        // EXTENSION: multiply the stored triangle of a (skew-)symmetric file as the whole matrix
                                    // (hip-csr only: spmv_hip_upload_csr_symmetric, include/spmv_hip_symmetric.h)
+    int vectors = 0;               // EXTENSION: > 0: Y += A X for that many vectors (hip-csr, one device: include/spmv_hip_multivec.h)
 };
 
 enum class SpmvFormat { csr, coo, coo_atomic, ell, hybrid };

@@ -17,6 +17,7 @@
 #include "util/json-ostreambuf.hpp"
 
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
+#include "spmv_hip_multivec.h" // (SPMV_HIP_MV_MAX_VECTORS of --vectors)
 
 #include <argp.h>
 #include <locale.h>
@@ -93,6 +94,7 @@ enum Key
     key_x,
     key_gpus,
     key_symmetric,
+    key_vectors,
 };
 
 bool parse_count(char const * arg, long long & out)
@@ -198,9 +200,26 @@ error_t parse_option(int key, char * arg, argp_state * state)
         else argp_error(state, "x: expected 'ones' or 'uniform'");
         break;
     case key_symmetric: a.spmv.symmetric = true; break;
+    case key_vectors:
+        if (!parse_count(arg, n) || n < 1 || n > SPMV_HIP_MV_MAX_VECTORS)
+            argp_error(state, "vectors: expected an integer from 1 to 16");
+        a.spmv.vectors = (int) n;
+        break;
     case ARGP_KEY_END:
         if (a.list_perf_events)
             break;
+        if (a.spmv.vectors > 0) {
+            // what --vectors runs on: hip-csr on one device (include/spmv_hip_multivec.h); anything else is refused here
+            if (a.spmv.symmetric)
+                argp_error(state, "--vectors cannot be combined with --symmetric: there is no multi-vector symmetric kernel");
+            if (a.kernel_type != KernelType::spmv || a.format != SpmvFormat::csr)
+                argp_error(state, "--vectors needs the CSR kernel on the GPU (--spmv-format hip-csr or --csr PATH): "
+                                  "there is no multi-vector COO, ELLPACK or hybrid kernel");
+            if (!a.hip && (!a.shortcut || a.device_given))
+                argp_error(state, "--vectors runs on the GPU only (--spmv-format hip-csr or --device hip): there is no CPU multi-vector kernel");
+            if (a.spmv.num_gpus > 1)
+                argp_error(state, "--vectors runs on one device (--gpus must be 1)");
+        }
         if (a.spmv.symmetric) {
             // what --symmetric runs on: the stored triangle of a (skew-)symmetric matrix, hip-csr on one device; anything else is
             // refused here rather than multiplied some other way
@@ -309,6 +328,9 @@ int main(int argc, char ** argv)
          "EXTENSION (hip-csr, one device): multiply the stored triangle of a symmetric or skew-symmetric file (or a synthetic:...:tril "
          "spec) as the whole matrix -- y += (T + T' - diag T) x, or (T - T') x -- reading every stored value once; --check then "
          "compares with the CPU CSR kernel on the expanded matrix.  Partial sums meet in atomics: not bit-reproducible", 2},
+        {"vectors", key_vectors, "K", 0,
+         "EXTENSION (hip-csr, one device): Y += A X for K = 1 ... 16 vectors in one multiply, every stored entry read once; column c "
+         "of X is x scaled by c + 1.  Flops count 2 nnz K; --check compares every column with the CPU CSR kernel", 2},
         {"matrix-cache", key_matrix_cache, "DIR", 0,
          "EXTENSION: keep the parsed entries of every matrix file in DIR and read them back next time "
          "(keyed by path, size and modification time; also: environment SPMV_MATRIX_CACHE)", 2},
@@ -398,13 +420,19 @@ int main(int argc, char ** argv)
         int count = 0;
         if (spmv_hip_device_count(&count) == 0 && count > 0)
             args.hip = true;
-        else if (!args.spmv.symmetric) // (--symmetric fails below: nothing runs in its place)
+        else if (!args.spmv.symmetric && args.spmv.vectors == 0) // (--symmetric / --vectors fail below: nothing runs in its place)
             std::cerr << "note: no usable HIP device: the CPU (OpenMP) kernel runs (--device hip makes this an error, --device cpu silences the note)\n";
     }
 
     if (args.spmv.symmetric && !args.hip) {
         std::cerr << "--symmetric: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU symmetric kernel "
                      "(nothing runs in its place)\n";
+        return EXIT_FAILURE;
+    }
+
+    if (args.spmv.vectors > 0 && !args.hip) {
+        std::cerr << "--vectors: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU multi-vector "
+                     "kernel (nothing runs in its place)\n";
         return EXIT_FAILURE;
     }
 
@@ -452,16 +480,36 @@ int main(int argc, char ** argv)
                 ref_options.symmetric = false;
                 ref_options.expand_symmetric = true;
             }
-            std::unique_ptr<Kernel> ref = make_spmv_kernel(SpmvFormat::csr, false, args.matrix_path, ref_options);
-            ref->init(one, std::cerr, false);
-            if (!xv.empty())
-                ref->set_x(xv);
-            for (int r = 0; r < args.profile + 1; ++r)
-                ref->run(one);
-            double const err = relative_error(kernel->result(), ref->result());
+            ref_options.vectors = 0;
+            double err = 0.0;
+            int const k = std::max(1, args.spmv.vectors);
+            std::vector<double> const got = kernel->result();
+            // --vectors: column c of Y against the CPU kernel with x scaled by c + 1, the worst column counts
+            for (int c = 0; c < k; ++c) {
+                std::unique_ptr<Kernel> ref = make_spmv_kernel(SpmvFormat::csr, false, args.matrix_path, ref_options);
+                ref->init(one, std::cerr, false);
+                if (!xv.empty() || args.spmv.vectors > 0) {
+                    std::vector<double> xc = xv.empty() ? std::vector<double>(ref->columns(), 1.0) : xv;
+                    for (double & e : xc)
+                        e *= c + 1.0;
+                    ref->set_x(xc);
+                }
+                for (int r = 0; r < args.profile + 1; ++r)
+                    ref->run(one);
+                std::vector<double> col = got;
+                if (args.spmv.vectors > 0) {
+                    col.assign(got.size() / (std::size_t) k, 0.0);
+                    for (std::size_t i = 0; i < col.size(); ++i)
+                        col[i] = got[i * (std::size_t) k + (std::size_t) c];
+                }
+                double const e = relative_error(col, ref->result());
+                if (!(e <= err)) // NaN sticks
+                    err = e;
+            }
             parity = ",\n\"parity\": {\"against\": \"csr-spmv (CPU, 1 thread)" +
-                std::string(args.spmv.symmetric ? " on the expanded matrix (expand_symmetry)" : "") + ", " + std::to_string(args.profile + 1) +
-                " accumulating runs\", \"max_relative_error\": ";
+                std::string(args.spmv.symmetric ? " on the expanded matrix (expand_symmetry)" : "") +
+                (args.spmv.vectors > 0 ? ", every one of the " + std::to_string(k) + " columns" : std::string()) + ", " +
+                std::to_string(args.profile + 1) + " accumulating runs\", \"max_relative_error\": ";
             char buf[64];
             if (std::isnan(err))
                 std::snprintf(buf, sizeof buf, "\"nan\"");

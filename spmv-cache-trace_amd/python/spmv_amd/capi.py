@@ -1,4 +1,5 @@
-"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h and spmv_hip_symmetric.h (the C ABI of libspmv_hip.so).
+"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h and spmv_hip_multivec.h (the C ABI
+of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -18,10 +19,10 @@ if os.environ.get("SPMV_HIP_EXPERIMENTS") == "1":
 elif os.environ.get("SPMV_HIP_EXPERIMENTS", "").endswith(".so"):  # an ablation build of tools/ablate.sh
     LIB_PATH = os.path.abspath(os.environ["SPMV_HIP_EXPERIMENTS"])
 # the drop-in boundary (what an adapter of the reference binds) and the headers that include it (tuning switches; Level 2;
-# the symmetric multiply of a stored triangle)
+# the symmetric multiply of a stored triangle; Y += A X for several vectors)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
-                                for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h")]
+                                for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -49,6 +50,8 @@ CSR_ALGORITHM_NAMES = {1: "scalar", 2: "vector", 3: "adaptive", 4: "wavetile"}
 SYMMETRIC, SKEW_SYMMETRIC = 1, 2
 TRIANGLE_MIXED, TRIANGLE_LOWER, TRIANGLE_UPPER, TRIANGLE_DIAGONAL = 0, 1, 2, 3
 TRIANGLE_NAMES = {0: "mixed", 1: "lower", 2: "upper", 3: "diagonal"}
+# spmv_hip_multivec.h
+MV_MAX_VECTORS = 16
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -108,6 +111,14 @@ SIGNATURES = {
     "spmv_hip_csr_symv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_sym_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
     "spmv_hip_sym_plan_destroy": (None, [_vp]),
+    "spmv_hip_mv_plan_csr": (C.c_int, [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, C.c_int, C.c_uint, _vp]),
+    "spmv_hip_csr_spmm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_hip_mv_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
+    "spmv_hip_mv_plan_destroy": (None, [_vp]),
+    "spmv_hip_set_block_x": (C.c_int, [_vp, C.c_int, _vp]),
+    "spmv_hip_set_block_y": (C.c_int, [_vp, C.c_int, _vp]),
+    "spmv_hip_get_block_y": (C.c_int, [_vp, C.c_int, _vp]),
+    "spmv_hip_run_block": (C.c_int, [_vp]),
 }
 
 
@@ -295,6 +306,29 @@ class Context:
         if sync:
             check(self.lib.spmv_hip_sync(self.h))
 
+    def set_block_x(self, X):
+        """X: (cols, k) host array, 1 <= k <= 16 (include/spmv_hip_multivec.h); a new k starts a new X / Y pair (Y zero)."""
+        X = _f64(X)
+        assert X.ndim == 2 and X.shape[0] == self.cols
+        check(self.lib.spmv_hip_set_block_x(self.h, X.shape[1], X.ctypes.data if X.size else _EMPTY_F64.ctypes.data))
+
+    def set_block_y(self, Y):
+        Y = _f64(Y)
+        assert Y.ndim == 2 and Y.shape[0] == self.rows
+        check(self.lib.spmv_hip_set_block_y(self.h, Y.shape[1], Y.ctypes.data if Y.size else _EMPTY_F64.ctypes.data))
+
+    def get_block_y(self, k):
+        Y = np.zeros((max(1, self.rows), k))
+        check(self.lib.spmv_hip_get_block_y(self.h, k, Y.ctypes.data))
+        return Y[:self.rows]
+
+    def run_block(self, runs=1, sync=True):
+        """Y += A X with the block vectors (the matrix of upload_csr)."""
+        for _ in range(runs):
+            check(self.lib.spmv_hip_run_block(self.h))
+        if sync:
+            check(self.lib.spmv_hip_sync(self.h))
+
     def flush_caches(self):
         """Evict the device's L2 and Infinity Cache (the device side of --flush-caches)."""
         check(self.lib.spmv_hip_flush_caches(self.h))
@@ -444,6 +478,66 @@ class SymPlan:
     def symv(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
         """y += (T + T' - diag(T)) x (or (T - T') x); raw device addresses, d_x != d_y."""
         check(self.lib.spmv_hip_csr_symv(self.h, d_row_ptr, d_col, d_val, d_x, d_y, stream))
+
+
+def _dev(a):
+    """(device address, leading dimension or None) of a torch tensor, or a raw address as it is."""
+    if hasattr(a, "data_ptr"):
+        if a.dim() == 2:
+            assert a.stride(1) == 1, "row-major rows needed (stride 1 along the vectors)"
+            return a.data_ptr(), a.stride(0)
+        return a.data_ptr(), None
+    return int(a), None
+
+
+class MvPlan:
+    """Level-2 plan of Y += A X for k vectors (spmv_hip_mv_plan_*): host row_ptr; X (cols, k) and Y (rows, k) row-major, as
+    torch tensors (column slices of wider ones included) or raw device addresses with explicit ldx / ldy."""
+
+    INFO_KEYS = ["rows", "cols", "k", "passes", "tiles", "long_rows", "streamed_bytes", "device_bytes", "stored_entries", "flags",
+                 "widest_pass"]
+
+    def __init__(self, rows, cols, host_row_ptr, k, flags=0, stream=0):
+        self.lib = load()
+        self.h = None
+        rp = _i32(host_row_ptr)
+        if len(rp) < rows + 1:
+            raise ValueError("host_row_ptr needs rows + 1 entries")
+        h = _vp()
+        check(self.lib.spmv_hip_mv_plan_csr(C.byref(h), rows, cols, rp.ctypes.data, k, flags, stream))
+        self.h = h
+        self.rows, self.cols, self.k = rows, cols, k
+
+    def close(self):
+        if self.h:
+            self.lib.spmv_hip_mv_plan_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.int64)
+        check(self.lib.spmv_hip_mv_plan_info(self.h, out, len(out)))
+        return dict(zip(self.INFO_KEYS, out.tolist()))
+
+    def spmm(self, d_row_ptr, d_col, d_val, X, Y, ldx=None, ldy=None, stream=0):
+        """Y += A X.  Tensors give their own address and leading dimension; raw addresses need ldx / ldy."""
+        (px, lx), (py, ly) = _dev(X), _dev(Y)
+        ldx = lx if ldx is None else ldx
+        ldy = ly if ldy is None else ldy
+        if ldx is None or ldy is None:
+            raise ValueError("ldx / ldy are needed for raw device addresses")
+        check(self.lib.spmv_hip_csr_spmm(self.h, _dev(d_row_ptr)[0], _dev(d_col)[0], _dev(d_val)[0], px, ldx, py, ldy, stream))
 
 
 def ipc_alloc(nbytes):
