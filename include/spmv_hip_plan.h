@@ -140,7 +140,9 @@ void spmv_hip_plan_destroy(spmv_hip_plan *plan);
  *             one 16-bit column list and one gather of x per group instead of per row, the values in place, the row sums of the
  *             plain tile bit for bit; a hint from row_ptr in spmv_hip_plan_csr, checked against the columns and marked by
  *             spmv_hip_plan_csr_repack; never with SPMV_HIP_FLAG_NO_BLOCK_TILES or a value dictionary)  [36] their entries
- *        [37] the rows per group of those tiles (0 = none) */
+ *        [37] the rows per group of those tiles (0 = none)
+ *        [38] chunks of stencil row runs (up to 128 rows each; 0 = none, see SPMV_HIP_FLAG_NO_STENCIL_RUNS)  [39] tiles merged
+ *             into those runs  [40] their entries */
 int spmv_hip_plan_info(const spmv_hip_plan *plan, int64_t *out, int n);
 
 /* y += A*x, CSR.  Replaces csr_spmv / csr_spmv_inner_loop

@@ -97,6 +97,12 @@ extern "C" {
                                              9-bit mask each (a 32-bit word per block instead of a column index per entry) if that
                                              takes at most 64 blocks holding 6 stored entries on average; with this flag such a tile
                                              keeps its 16-bit columns (round 4's behaviour: one broken block demotes its tile) */
+#define SPMV_HIP_FLAG_NO_STENCIL_RUNS 0x80000000u /* plan: no stencil row runs.  By default, when most entries of a plan without a value
+                                             dictionary, x windows or block / segment windows lie in shifted, uniform tiles of rows of 5
+                                             entries that follow one pattern record (the interior of a structured grid, values read as
+                                             doubles), maximal runs of such tiles are cut into chunks of up to 128 rows and multiplied by a
+                                             few waves per CU that walk many chunks each (values by LDS-DMA); the other tiles take the
+                                             default kernel in a second launch.  Same sums, same bits (plan_info[38..40]) */
 /* 0x4000000u and 0x10000000u are not flags of this library: two kernel families that were measured SLOWER than the paths they
  * were meant to replace (hub columns for web graphs, 26.6 vs 23.9 us; a lane group per row for stencil rows of 17 ... 64
  * entries, 797 vs 740 us: DESIGN.md sections 3.3, 3.1b) were retired from the product library in round 5 and are

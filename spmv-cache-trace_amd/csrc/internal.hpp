@@ -55,7 +55,8 @@ constexpr unsigned kKnownFlags = SPMV_HIP_FLAG_XCD_REMAP | SPMV_HIP_FLAG_EXACT_O
     SPMV_HIP_FLAG_ROWS128 | SPMV_HIP_FLAG_ELL_COLUMN_MAJOR | SPMV_HIP_FLAG_NO_SHIFTED_TILES | SPMV_HIP_FLAG_NO_X_WINDOW |
     SPMV_HIP_FLAG_NO_COLUMN_PANELS | SPMV_HIP_FLAG_VERIFY_PLAN | SPMV_HIP_FLAG_NO_BALANCED_TILES | SPMV_HIP_FLAG_NO_RUN_EVENTS | SPMV_HIP_FLAG_NO_VALUE_INDEX |
     SPMV_HIP_FLAG_PEER_GATHER | SPMV_HIP_FLAG_BALANCE_ENTRIES | SPMV_HIP_FLAG_NO_SEGMENT_WINDOW | SPMV_HIP_FLAG_FUSED_PEER_STORE |
-    SPMV_HIP_FLAG_NO_BLOCK_TILES | SPMV_HIP_FLAG_NO_MULTI_WINDOW | SPMV_HIP_FLAG_NO_MASKED_BLOCKS | SPMV_HIP_FLAG_PIPELINE_GATHER
+    SPMV_HIP_FLAG_NO_BLOCK_TILES | SPMV_HIP_FLAG_NO_MULTI_WINDOW | SPMV_HIP_FLAG_NO_MASKED_BLOCKS | SPMV_HIP_FLAG_PIPELINE_GATHER |
+    SPMV_HIP_FLAG_NO_STENCIL_RUNS
 #ifdef SPMV_HIP_EXPERIMENTS
     | 0x2000u | 0x4000u | 0x30000u // timing experiments of tools/kernel_sweep.py (libspmv_hip_experiments.so only)
     | SPMV_HIP_FLAG_HUB_COLUMNS | SPMV_HIP_FLAG_ROW_GROUPS // kernel families that were measured SLOWER than the default path (below)
@@ -114,6 +115,12 @@ struct spmv_hip_plan {
     int blockwin_tiles = 0;
     int32_t * d_rest_tiles = nullptr; // with block / segment windows: the tiles NOT marked for them (what csr_wavetile_kernel<LIST> multiplies)
     int nrest_tiles = 0;
+    // stencil row runs (csr_runs.hpp): chunks of up to 128 rows of runs of stencil-row tiles that share a row length and a
+    // pattern record, multiplied by csr_wavetile_kernel_runs; every other tile is in d_run_rest (csr_wavetile_kernel<LIST>)
+    int4 * d_run_chunks = nullptr; // {first row, first entry, rows, pattern}
+    int32_t * d_run_rest = nullptr;
+    int nrun_chunks = 0, nrun_rest = 0, run_len = 0, run_tiles = 0;
+    long long run_entries = 0;
     // row-group plans (csr_rowgroup.hpp): the tiles csr_rowgroup_kernel multiplies, and the others (csr_wavetile_kernel<LIST>)
     int32_t * d_group_tiles = nullptr, * d_group_rest = nullptr;
     int ngroup_tiles = 0, ngroup_rest = 0;
@@ -258,6 +265,7 @@ int plan_csr_internal(spmv_hip_plan ** out, int32_t rows, int32_t cols, const in
 int device_index_check(const int32_t * d_idx, long long n, int limit, bool want_sorted, bool * bad, bool * sorted, hipStream_t s);
 int verify_plan(const spmv_hip_plan * pl, const int32_t * d_column_index, hipStream_t s);
 int verify_plan_values(const spmv_hip_plan * pl, const double * d_value, hipStream_t s);
+void drop_stencil_runs(spmv_hip_plan * pl);
 
 // context.hip
 void free_ctx_matrix(spmv_hip_ctx * c);

@@ -242,6 +242,20 @@ static int csr_spmv_launch(const spmv_hip_plan * pl, const int32_t * p, const in
                     hipLaunchKernelGGL((spmv::csr_wavetile_kernel<512, true, false, false, 0, 0, false, false, false, true>), grid, dim3(256), 0, s,
                                        pl->nrest_tiles, pl->d_tiles, p, j, pl->d_col16, a, x, y_in, y, pl->nnz, pl->cols, exact, pl->d_patterns,
                                        spmv::PanelInfo{}, (const uint8_t *) nullptr, (const double *) nullptr, 0, spmv::PeerY{}, pl->d_rest_tiles);
+            } else if (pl->d_run_chunks && pl->run_len == 5 && c16 && x32 && !xcd && !peers && !pl->d_group_tiles && !(pl->nvalues > 0 && pl->values_from == a)
+                       && spmvi::aligned16(a)
+#ifdef SPMV_HIP_EXPERIMENTS
+                       && !abl
+#endif
+            ) {
+                // stencil row runs (csr_runs.hpp): a wave per chunk of 128 rows (a grid of resident waves that walk the chunks measured
+                // 212 against 188 us on Poisson 4096^2; a wave per chunk 180), then the other tiles
+                const dim3 grid((unsigned) ((pl->nrun_chunks + spmv::kRunWaves - 1) / spmv::kRunWaves));
+                hipLaunchKernelGGL((spmv::csr_wavetile_kernel_runs<5>), grid, dim3(256), 0, s, pl->nrun_chunks, pl->d_run_chunks, pl->d_patterns, a, x, y_in, y);
+                if (pl->nrun_rest > 0)
+                    hipLaunchKernelGGL((spmv::csr_wavetile_kernel<512, true, true, false, 0, 0, false, false, false, true>), dim3((unsigned) ((pl->nrun_rest + 3) / 4)),
+                                       dim3(256), 0, s, pl->nrun_rest, pl->d_tiles, p, j, pl->d_col16, a, x, y_in, y, pl->nnz, pl->cols, exact, pl->d_patterns,
+                                       spmv::PanelInfo{}, (const uint8_t *) nullptr, (const double *) nullptr, 0, spmv::PeerY{}, pl->d_run_rest);
             } else
 #ifdef SPMV_HIP_EXPERIMENTS
             if (pl->d_group_tiles && c16 && x32 && !xcd && !exact_order && pl->tile == 512 && (!peers || pl->split_rows == 0)) {

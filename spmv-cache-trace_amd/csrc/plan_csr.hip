@@ -135,6 +135,101 @@ int verify_plan(const spmv_hip_plan * pl, const int32_t * d_column_index, hipStr
     return SPMV_HIP_OK;
 }
 
+void drop_stencil_runs(spmv_hip_plan * pl)
+{
+    for (void * q : {(void *) pl->d_run_chunks, (void *) pl->d_run_rest})
+        if (q)
+            (void) hipFree(q);
+    pl->d_run_chunks = nullptr;
+    pl->d_run_rest = nullptr;
+    pl->nrun_chunks = pl->nrun_rest = pl->run_len = pl->run_tiles = 0;
+    pl->run_entries = 0;
+}
+
+// Stencil row runs (csr_runs.hpp).  Only for the launch that would otherwise multiply every tile with the plain default
+// kernel (launch.hip checks the launch-time half: 16-bit stream of this column array, no dictionary in use, no panels, no
+// peers, 16-byte aligned values).  A tile joins a run when the default kernel would take its `stencil_values` path: a fast
+// stream tile, shifted, uniform, one lane per row, its rows of L = 5 entries, columns from a pattern record, no
+// other class on top; a run is a maximal sequence of such tiles with the same L and pattern record (contiguous rows and
+// entries by construction).  Runs are cut into chunks of 128 rows (never one of a single row); the other tiles keep their
+// descriptors and go to the rest list.  Nothing changes what a multiply streams: plan_account's numbers stay as they are.
+static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, bool compressed)
+{
+    drop_stencil_runs(pl);
+    const bool exact_order = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) != 0;
+    const bool xwin_launch = !(pl->flags & SPMV_HIP_FLAG_NO_X_WINDOW) && (!exact_order || pl->longest_tile_row <= 32)
+        && 2 * (long long) pl->xwin_tiles > pl->ntiles;
+    if ((pl->flags & (SPMV_HIP_FLAG_NO_STENCIL_RUNS | SPMV_HIP_FLAG_XCD_REMAP)) || !compressed || pl->nvalues > 0 || pl->balanced
+        || pl->inner || pl->d_blocks || pl->d_segblocks || pl->tile != 512 || pl->npatterns == 0 || pl->cols >= (1 << 29) || xwin_launch
+        || pl->algorithm != SPMV_HIP_CSR_WAVETILE || pl->ntiles == 0)
+        return SPMV_HIP_OK;
+    const int ntiles = pl->ntiles;
+    auto run_len = [&](int w) -> int { // L if tile w belongs in a run, else 0
+        const int4 t = d[(size_t) w];
+        const int meta = t.z;
+        const int k0 = t.y, k1 = d[(size_t) w + 1].y;
+        const int L = meta & 0xFFFF;
+        const int need = spmv::kTileMetaFast | spmv::kTileMetaShifted | spmv::kTileMetaUniform | spmv::kTileMetaPattern;
+        if ((t.x & spmv::kTileFlagPartial) || k1 <= k0 || (meta & need) != need || ((meta >> spmv::kTileMetaLanesShift) & 7) != 0
+            || (meta & (spmv::kTileMetaBlockWin | spmv::kTileMetaBlock3)) || spmv::is_masked_stencil_tile(meta) || k1 - (k0 & ~3) > 512)
+            return 0;
+        return L == 5 ? L : 0; // (7-point rows were measured slower: 250 against 240 us on a 256^3 grid)
+    };
+    constexpr int L = 5;
+    long long run_candidates = 0;
+    for (int w = 0; w < ntiles; ++w)
+        if (run_len(w))
+            run_candidates += (long long) d[(size_t) w + 1].y - d[(size_t) w].y;
+    if (2 * run_candidates <= (long long) pl->nnz)
+        return SPMV_HIP_OK; // runs pay only where they cover most of the matrix
+    std::vector<int4> chunks;
+    std::vector<int32_t> rest;
+    long long entries = 0;
+    int tiles = 0;
+    for (int w = 0; w < ntiles;) {
+        if (run_len(w) != L) {
+            rest.push_back(w++);
+            continue;
+        }
+        const int pat = d[(size_t) w].w;
+        int e = w + 1;
+        while (e < ntiles && run_len(e) == L && d[(size_t) e].w == pat)
+            ++e;
+        const int r0 = d[(size_t) w].x, r1 = d[(size_t) e].x & ~spmv::kTileFlagPartial;
+        const int k0 = d[(size_t) w].y;
+        if (r1 - r0 < 2) {
+            for (int q = w; q < e; ++q)
+                rest.push_back(q);
+        } else {
+            for (int r = r0; r < r1;) {
+                int n = std::min(spmv::kRunChunkRows, r1 - r);
+                if (r1 - r - n == 1)
+                    --n; // no chunk of one row: 127 + 2
+                chunks.push_back(int4{r, k0 + (r - r0) * L, n, pat});
+                r += n;
+            }
+            entries += (long long) d[(size_t) e].y - k0;
+            tiles += e - w;
+        }
+        w = e;
+    }
+    if (chunks.empty())
+        return SPMV_HIP_OK;
+    HIP_TRY(hipMalloc((void **) &pl->d_run_chunks, chunks.size() * sizeof(int4)));
+    HIP_TRY(hipMemcpy(pl->d_run_chunks, chunks.data(), chunks.size() * sizeof(int4), hipMemcpyHostToDevice));
+    pl->nrun_chunks = (int) chunks.size();
+    pl->nrun_rest = (int) rest.size();
+    if (!rest.empty()) {
+        rest.resize((rest.size() + 3) & ~(size_t) 3, rest.back()); // padded to whole workgroups (never read past nrun_rest)
+        HIP_TRY(hipMalloc((void **) &pl->d_run_rest, rest.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(pl->d_run_rest, rest.data(), rest.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    pl->run_len = L;
+    pl->run_tiles = tiles;
+    pl->run_entries = entries;
+    return SPMV_HIP_OK;
+}
+
 // Bytes one multiply streams with the tile classes chosen (bookkeeping for the roofline report):
 // values 8 B per entry; columns 4 B (wide), 2 B (16-bit), one first row (shifted) or nothing
 // (shifted with a pattern); row_ptr 4 B per row of a non-uniform tile; y 16 B per row; x once;
@@ -144,6 +239,7 @@ int plan_account(spmv_hip_plan * pl, bool compressed)
     const long long algorithmic = 12LL * pl->nnz + 4LL * (pl->rows + 1LL) + 16LL * pl->rows + 8LL * pl->cols;
     pl->streamed_bytes = algorithmic;
     pl->shifted_entries = pl->narrow_entries = pl->uniform_rows = 0;
+    drop_stencil_runs(pl);
     if (pl->algorithm != SPMV_HIP_CSR_WAVETILE || pl->ntiles == 0)
         return SPMV_HIP_OK;
     // (the dictionary launch may have its own descriptors: runs of constant-row tiles re-cut into tiles of 128 rows)
@@ -222,6 +318,11 @@ int plan_account(spmv_hip_plan * pl, bool compressed)
         pl->nrest_tiles = 0;
         for (int w = 0; w < pl->ntiles; ++w)
             pl->nrest_tiles += !(d[(size_t) w].z & spmv::kTileMetaBlockWin);
+    }
+    {
+        int rc = build_stencil_runs(pl, d, compressed); // (returns at once under a value dictionary)
+        if (rc != SPMV_HIP_OK)
+            return rc;
     }
     // row-group plans (csr_rowgroup.hpp, opt-in): made anew after every change of the tile marks
     for (int32_t ** q : {&pl->d_group_tiles, &pl->d_group_rest})
@@ -1015,6 +1116,7 @@ void spmv_hip_plan_destroy(spmv_hip_plan * pl)
         (void) hipFree(pl->d_segblocks);
     if (pl->d_rest_tiles)
         (void) hipFree(pl->d_rest_tiles);
+    drop_stencil_runs(pl);
     if (pl->d_group_tiles)
         (void) hipFree(pl->d_group_tiles);
     if (pl->d_group_rest)
@@ -1410,6 +1512,7 @@ static int rebuild_tiles(spmv_hip_plan * pl, const int32_t * d_row_ptr, const in
             (void) hipFree(q);
     pl->d_tiles = nullptr; pl->d_col16 = nullptr; pl->d_patterns = nullptr; pl->d_blocks = nullptr; pl->d_segblocks = nullptr;
     pl->d_rest_tiles = nullptr;
+    drop_stencil_runs(pl);
     pl->ntiles = pl->nblk = pl->workgroups = 0;
     pl->narrow_tiles = pl->shifted_tiles = pl->xwin_tiles = pl->longest_tile_row = pl->spread_tiles = 0;
     pl->nblocks16 = pl->blockwin_tiles = pl->nrest_tiles = pl->nsegblocks = pl->segwin_tiles = pl->segwin_slots = pl->npatterns = 0;
@@ -2101,7 +2204,7 @@ int spmv_hip_plan_info(const spmv_hip_plan * pl, int64_t * out, int n)
 {
     if (!pl || !out || n < 0)
         return fail(SPMV_HIP_ERR_INVALID, "plan/out null");
-    const int64_t v[38] = {pl->algorithm, pl->lanes_per_row, pl->workgroups, pl->nblk,
+    const int64_t v[41] = {pl->algorithm, pl->lanes_per_row, pl->workgroups, pl->nblk,
                            pl->long_blocks, pl->rows, pl->nnz, (int64_t) pl->meta_bytes, pl->narrow_tiles,
                            pl->uniform_tiles, pl->shifted_tiles, pl->xwin_tiles, pl->blockwin_tiles,
                            pl->inner ? pl->inner->ntiles : 0, pl->streamed_bytes, pl->shifted_entries,
@@ -2112,8 +2215,8 @@ int spmv_hip_plan_info(const spmv_hip_plan * pl, int64_t * out, int n)
                            pl->ngroup_tiles, pl->nvalues > 0 ? 0 : pl->masked_block_tiles, pl->nvalues > 0 ? 0 : pl->masked_block_entries,
                            pl->stencil_mask_tiles, pl->stencil_mask_entries,
                            pl->nvalues > 0 ? 0 : pl->colshare_tiles, pl->nvalues > 0 ? 0 : pl->colshare_entries,
-                           pl->colshare_tiles > 0 ? pl->block_hint : 0};
-    for (int i = 0; i < n && i < 38; ++i)
+                           pl->colshare_tiles > 0 ? pl->block_hint : 0, pl->nrun_chunks, pl->run_tiles, pl->run_entries};
+    for (int i = 0; i < n && i < 41; ++i)
         out[i] = v[i];
     return SPMV_HIP_OK;
 }

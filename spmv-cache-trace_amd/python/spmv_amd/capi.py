@@ -44,6 +44,7 @@ FLAG_NO_BLOCK_TILES = 0x2000000
 FLAG_HUB_COLUMNS = 0x4000000  # libspmv_hip_experiments.so only (retired from the product: csrc/internal.hpp)
 FLAG_NO_MULTI_WINDOW = 0x8000000
 FLAG_NO_MASKED_BLOCKS = 0x20000000
+FLAG_NO_STENCIL_RUNS = 0x80000000  # no stencil row runs (csr_runs.hpp): every tile in the default kernel's launch
 FLAG_ROW_GROUPS = 0x10000000  # libspmv_hip_experiments.so only (retired from the product: csrc/internal.hpp)
 CSR_ALGORITHM_NAMES = {1: "scalar", 2: "vector", 3: "adaptive", 4: "wavetile"}
 # spmv_hip_symmetric.h
@@ -375,14 +376,14 @@ class CsrPlan:
             pass
 
     def info(self):
-        out = np.zeros(38, dtype=np.int64)
-        check(self.lib.spmv_hip_plan_info(self.h, out, 38))
+        out = np.zeros(41, dtype=np.int64)
+        check(self.lib.spmv_hip_plan_info(self.h, out, 41))
         keys = ["algorithm", "lanes_per_row", "workgroups", "row_blocks", "long_blocks", "rows",
                 "nnz", "meta_bytes", "narrow_tiles", "uniform_tiles", "shifted_tiles", "xwin_tiles", "blockwin_tiles", "panel_tiles",
                 "streamed_bytes", "shifted_entries", "narrow_entries", "uniform_rows", "value_snapshot", "balanced", "indexed_values",
                 "segwin_tiles", "segwin_slots", "value_row_tiles", "dictionary_launch_tiles", "block_tiles", "block_entries", "hub_columns", "hub_entries", "multi_window_tiles", "row_group_tiles",
                 "masked_block_tiles", "masked_block_entries", "stencil_mask_tiles", "stencil_mask_entries",
-                "group_tiles", "group_entries", "group_rows"]
+                "group_tiles", "group_entries", "group_rows", "run_chunks", "run_tiles", "run_entries"]
         return dict(zip(keys, out.tolist()))
 
     def confirm_blocks(self, d_row_ptr, d_col, host_row_ptr=None, stream=0):
