@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X SpMV path.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python bench.py --workload queen|kkt|webbase|powerlaw [--format csr|coo|ell|hybrid]
     python bench.py --matrix Queen_4147.tar.gz [--expand-symmetric] [--format ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -22,6 +22,12 @@ Prints ONE JSON line on rank 0.  `value` = 2*Z*K / t in GFLOP/s (whole job); `ms
 --dump-outputs DIR writes y as the K timed steps left it (warm-up + K multiplies accumulated from y = 0) to DIR/y.npy,
 float64; beyond 64 MB a fixed seeded sample of rows, their numbers in DIR/y_rows.npy.  Inputs are seeded: the same
 arguments give the same inputs on every run, so two builds can be compared output for output.
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, dumps y if asked and prints the line
+(config, the roofline figures of the timed launch itself, build).  Everything else described below -- the STREAM triad,
+`cold`, `plan_ms`, `compressed`, PMC `traffic`, the companions, `drop_in_multi_gpu`, `cpu_baseline` and its parity gate,
+`host_boundary`, `reference_protocol` and, for N > 1, the collective alone, the gather check, the link probe and the deferred
+gather -- runs only with --full.  The --no-* switches below pick legs out of a --full run.
 
 The timed launch READS THE VALUE ARRAY (plan flag SPMV_HIP_FLAG_NO_VALUE_INDEX: what the kernel does for a matrix of this
 structure with arbitrary values), and `roofline` follows SURVEY section 8(d) to the letter: `achieved` = ALGORITHMIC bytes
@@ -143,6 +149,10 @@ def parse_args():
     ap.add_argument("--lanes", type=int, default=0)
     ap.add_argument("--xcd-remap", action="store_true")
     ap.add_argument("--flags", type=lambda v: int(v, 0), default=0, help="extra SPMV_HIP_FLAG_* bits")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, run every other measurement and check of the line (CPU baseline and parity, cold "
+                         "and compressed launches, plan cost, triad, PMC traffic, companions, the drop-in and reference-protocol legs, "
+                         "N > 1: gather check, link probe); a plain run times the steps and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all host cores visible to this process")
@@ -182,7 +192,7 @@ def parse_args():
     ap.add_argument("--no-cold", action="store_true", help="skip the flushed-cache timing of the headline launch")
     ap.add_argument("--no-config3", action="store_true",
                     help="skip the companion measurement of BASELINE configs[3] (the nlpkkt200-like KKT matrix, the configuration "
-                         "BASELINE.json partitions over 8 GPUs) that the default workload's line carries as `config3_kkt`")
+                         "BASELINE.json partitions over 8 GPUs) that the default workload's --full line carries as `config3_kkt`")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo is for rehearsing N > 1 on a box with one GPU")
     ap.add_argument("--share-gpu", action="store_true",
@@ -1255,7 +1265,9 @@ def main():
     setup_s = time.perf_counter() - t_setup
 
     # ---- one multiply into a zero y, kept for the cpu_baseline leg (the only place the checker
-    # libraries under oracle/ are loaded), which compares it with the CPU kernel's y ------------
+    # libraries under oracle/ are loaded), which compares it with the CPU kernel's y.  A plain run
+    # makes and fetches it too, unused: the timed steps start from the same device state as in a
+    # --full run (the plan's first multiply re-checks its checksums; the fetch idles the device) ----------
     y_check = None
     if world == 1 and not use_dist and not args.no_cpu_baseline and not args.no_parity_check:
         if fmt == "csr":
@@ -1386,33 +1398,34 @@ def main():
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
     elapsed_max, kern_ms_max = stats.tolist()
 
-    # ---- the empirical denominator: STREAM triad on 3 x 512 MiB in the same process -------------
+    # ---- --full: the empirical denominator, STREAM triad on 3 x 512 MiB in the same process -------------
     triad_gbs = None
-    try:
-        nt = 64 * 1024 * 1024
-        ta = torch.zeros(nt, dtype=torch.float64, device=device)
-        tb = torch.ones(nt, dtype=torch.float64, device=device)
-        tc_ = torch.ones(nt, dtype=torch.float64, device=device)
-        for _ in range(3):
-            capi.triad(nt, ta.data_ptr(), tb.data_ptr(), tc_.data_ptr(), 3.1, stream)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            capi.triad(nt, ta.data_ptr(), tb.data_ptr(), tc_.data_ptr(), 3.1, stream)
-        e1.record()
-        torch.cuda.synchronize()
-        triad_gbs = 24.0 * nt * 20 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del ta, tb, tc_
-    except (RuntimeError, capi.SpmvHipError):
-        triad_gbs = None
+    if args.full:
+        try:
+            nt = 64 * 1024 * 1024
+            ta = torch.zeros(nt, dtype=torch.float64, device=device)
+            tb = torch.ones(nt, dtype=torch.float64, device=device)
+            tc_ = torch.ones(nt, dtype=torch.float64, device=device)
+            for _ in range(3):
+                capi.triad(nt, ta.data_ptr(), tb.data_ptr(), tc_.data_ptr(), 3.1, stream)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                capi.triad(nt, ta.data_ptr(), tb.data_ptr(), tc_.data_ptr(), 3.1, stream)
+            e1.record()
+            torch.cuda.synchronize()
+            triad_gbs = 24.0 * nt * 20 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del ta, tb, tc_
+        except (RuntimeError, capi.SpmvHipError):
+            triad_gbs = None
 
-    # ---- beside the headline launch: its cold time, what its plan cost, and the product's default plan --------------------
+    # ---- --full, beside the headline launch: its cold time, what its plan cost, and the product's default plan -------------
     # The timed plan reads the value array.  For a matrix with <= 128 distinct values (this Poisson operator has two) the
     # library by default builds a value dictionary and the launch streams one index byte per entry -- or, in constant-row
     # tiles, none -- instead of eight: far fewer bytes than SURVEY 8(d) prices, so that launch is reported BESIDE the
     # roofline row, as `compressed`: same process, same device arrays, same K and warm-up, bit-identical y.
     cold = plan_ms = compressed = None
-    single = fmt == "csr" and world == 1 and not use_dist
+    single = fmt == "csr" and world == 1 and not use_dist and args.full
     flusher = None
     if single and not args.no_cold:
         flusher = CacheFlusher(torch, device)
@@ -1465,10 +1478,10 @@ def main():
     del flusher
     torch.cuda.empty_cache()
 
-    # N > 1: the collective on its own (after the timed region, not part of `value`): a few
+    # N > 1, --full: the collective on its own (after the timed region, not part of `value`): a few
     # blocking all-gathers, max over ranks, so the line shows where a step's time goes.
     gather_us = None
-    if use_dist:
+    if use_dist and args.full:
         op.finish()
         rc_op = ops["rccl"] if fmt == "csr" else op
         times = []
@@ -1483,13 +1496,13 @@ def main():
         dist.all_reduce(gt, op=dist.ReduceOp.MAX)
         gather_us = gt.item() * 1e6
 
-    # N > 1: the gathered y must hold what the OTHER ranks computed.  Rank 0 recomputes a strip of
+    # N > 1, --full: the gathered y must hold what the OTHER ranks computed.  Rank 0 recomputes a strip of
     # the last rank's rows on its own GPU (product kernel, one multiply) and compares it with the
     # gathered segment, which has accumulated warm-up + K multiplies.
     gather_check = None
     if use_dist:
         op.finish()  # every rank (the peer schemes meet at a barrier here); below, rank 0 reads its vector without one
-    if use_dist and world > 1 and rank == 0 and spec is not None and spec.startswith("synthetic:"):
+    if use_dist and args.full and world > 1 and rank == 0 and spec is not None and spec.startswith("synthetic:"):
         ob, oe = ranges[world - 1] if ranges is not None else partition.row_range(rows, world - 1, world)
         strip = min(4096, oe - ob)
         S = hostapi.load_csr_rows(spec, ob, ob + strip)
@@ -1507,7 +1520,7 @@ def main():
     if use_dist:
         dist.barrier()  # rank 0 is done reading its vector: the ranks may multiply on
 
-    if use_dist and schemes is not None:
+    if use_dist and args.full and schemes is not None:
         # per scheme: the local multiply alone (no delivery of any kind), the delivery alone where it is a launch
         # or a call of its own, and the whole step from the calibration above
         def events_us(fn, n=10):
@@ -1537,11 +1550,11 @@ def main():
         for o in ops.values():
             o.finish()
 
-    # N > 1, for information only (never `value`): the same K multiplies with ONE all-gather after the
+    # N > 1, --full, for information only (never `value`): the same K multiplies with ONE all-gather after the
     # last of them -- what a caller pays who, like the reference's timed loop, looks at y only after
     # the loop.  `value` above gathers after every multiply.
     deferred = None
-    if use_dist:
+    if use_dist and args.full:
         dop = ops["rccl"] if fmt == "csr" else op
         torch.cuda.synchronize()
         dist.barrier()
@@ -1556,11 +1569,11 @@ def main():
         deferred = {"steps": args.steps, "all_gathers": 1, "ms_total": round(dt.item() * 1e3, 4),
                     "gflops": round(2.0 * nnz * args.steps / dt.item() / 1e9, 2)}
 
-    # ---- N > 1: what do the links deliver?  (after the timed region; a few ms; never part of `value`) -----------------------
+    # ---- N > 1, --full: what do the links deliver?  (after the timed region; a few ms; never part of `value`) ----------------
     # The y segments travel as stores into the other ranks' vectors (or as RCCL's transfers over the same links): the rate of
     # exactly those stores, per peer and with all peers at once, so that the line explains its own step time.
     probe = None
-    if use_dist and fmt == "csr":
+    if use_dist and args.full and fmt == "csr":
         po = ops.get("peer-push") or ops.get("peer-fused")
         if po is None or world < 2:
             probe = {"link_probe_gbs": None, "why": peer_note or ("one rank" if world < 2 else "no peer-store operator was set up (--gather rccl)")}
@@ -1583,11 +1596,11 @@ def main():
                                 "per link and direction), 5 passes per peer after one untimed pass; then into all peers at once",
                      "same_device": bool(args.share_gpu)}
 
-    # ---- companion: BASELINE configs[3] on the same ranks ----------------------------------------------------------------
+    # ---- --full, companion: BASELINE configs[3] on the same ranks ---------------------------------------------------------
     # The headline workload (configs[1], Poisson: 5 entries per row) cannot scale strongly with a replicated y; the
     # configuration BASELINE.json partitions over 8 GPUs is nlpkkt200 (27 entries per row).  So that a run at N = 1, 2, 4, 8
-    # also says what THAT matrix does on the same ranks with the same gather scheme, the default line carries a short
-    # measurement of its stand-in (30 timed steps after 10 warm-up steps; never part of `value`).
+    # also says what THAT matrix does on the same ranks with the same gather scheme, the default workload's --full line carries
+    # a short measurement of its stand-in (30 timed steps after 10 warm-up steps; never part of `value`).
     def partitioned_companion(spec3, label3, note3):
         import argparse as _ap
         a3 = _ap.Namespace(**vars(args))
@@ -1676,7 +1689,7 @@ def main():
 
     config3 = None
     north_star = {}
-    if fmt == "csr" and args.matrix is None and args.workload == "poisson2d" and args.grid == 4096 and not args.no_config3:
+    if args.full and fmt == "csr" and args.matrix is None and args.workload == "poisson2d" and args.grid == 4096 and not args.no_config3:
         config3 = partitioned_companion("synthetic:kkt:200", "kkt-27pt-200^3 (nlpkkt200-like)",
                                         "whole-job GFLOP/s of BASELINE configs[3]'s stand-in on these ranks; parity of this matrix and "
                                         "path: tests/test_gpu_fullsize.py, tests/test_gpu_peer.py")
@@ -1688,10 +1701,10 @@ def main():
             north_star["random"] = partitioned_companion("synthetic:random:4000000,24,3", "random-4M-24perrow",
                                                          "whole-job GFLOP/s on these ranks; parity: tests/test_gpu_parity.py, bench.py --workload random24")
 
-    # ---- companions: BASELINE configs[2] and [4] on this GPU (default workload, one GPU) -------------------------------------
+    # ---- --full, companions: BASELINE configs[2] and [4] on this GPU (default workload, one GPU) ------------------------------
     companions = {}
-    if (fmt == "csr" and args.matrix is None and args.workload == "poisson2d" and args.grid == 4096 and world == 1 and not use_dist
-            and not args.no_companions):
+    if (args.full and fmt == "csr" and args.matrix is None and args.workload == "poisson2d" and args.grid == 4096 and world == 1
+            and not use_dist and not args.no_companions):
         companions["config2_queen"] = companion(torch, capi, hostapi, synth, args, device, stream, "synthetic:queen", "csr",
                                                 "queen-like 110x71x177 mesh x 3 dof (Queen_4147-like), csr", flags, algo)
         # round 6: the reference's DEFAULT semantics for the two SuiteSparse files -- a `symmetric` file's stored
@@ -1706,9 +1719,9 @@ def main():
             for f in ("coo", "hybrid", "csr")}
         companions["config4_webbase"]["ell"] = "not representable: rows x longest row overflows int32, the converter throws like the reference's (ell-matrix.cpp:201-205)"
 
-    # ---- the drop-in's own multi-GPU path (one process over all devices) beside the one-process-per-GPU measurement ------------
+    # ---- --full: the drop-in's own multi-GPU path (one process over all devices) beside the one-process-per-GPU measurement -----
     drop_in = None
-    if fmt == "csr" and spec is not None and not args.no_drop_in and not args.force_collective:
+    if args.full and fmt == "csr" and spec is not None and not args.no_drop_in and not args.force_collective:
         dspecs = [("headline", spec)]
         if world > 1 and config3 is not None and not args.share_gpu:  # (a rehearsal on one shared device keeps to the headline matrix)
             dspecs.append(("config3_kkt", "synthetic:kkt:200"))
@@ -1857,10 +1870,10 @@ def main():
         out["build"] = build
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        tr = pmc_traffic(kernel_name, wname, int(local_bytes), out["roofline"].get("streamed_bytes_per_launch"), build, kern_s * 1e6)
+        tr = pmc_traffic(kernel_name, wname, int(local_bytes), out["roofline"].get("streamed_bytes_per_launch"), build, kern_s * 1e6) if args.full else None
         live = None
         under_profiler = any("ROCPROF" in k or k.startswith("ROCP_") for k in os.environ)  # (this run is itself a rocprofv3 child: no nesting)
-        if world == 1 and not use_dist and fmt == "csr" and spec is not None and not args.no_live_pmc and code == 0 and not under_profiler:
+        if args.full and world == 1 and not use_dist and fmt == "csr" and spec is not None and not args.no_live_pmc and code == 0 and not under_profiler:
             live = live_pmc_traffic(args, MULTIPLY_KERNELS, streamed)
         if live is not None and "traffic" in live:
             # measured in THIS run, on THIS box, with the library that was just timed; the committed profile (another run, another
@@ -1893,19 +1906,19 @@ def main():
             if live is not None:
                 out["roofline"]["traffic_live"] = live
             out["roofline"]["traffic_source"] = ("none: no committed profiles/*_summary.json of this workload was taken with device "
-                                                 "sources %s" % build["source_sha256"])
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+                                                 "sources %s" % build["source_sha256"]) if args.full else "not looked for: bench.py --full"
+        if args.full and world == 1 and not use_dist and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(args, fmt, rows, cols, host_arrays, x, y_check)
             if out["parity"] and not out["parity"]["pass"]:
                 code, message = 1, "bench.py: parity check failed: max relative error %s > 1e-10" % out["parity"]["max_rel_err"]
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not use_dist and fmt == "csr" and not args.no_host_boundary and host_arrays is not None and code == 0:
+        if args.full and world == 1 and not use_dist and fmt == "csr" and not args.no_host_boundary and host_arrays is not None and code == 0:
             try:
                 out["host_boundary"] = host_boundary(capi, device.index or 0, rows, cols, host_arrays, x, nnz)
             except Exception as e:  # reported, never fatal: the line's value does not depend on it
                 out["host_boundary"] = {"error": str(e)[:200]}
-        if world == 1 and not use_dist and not args.no_reference_protocol and code == 0:
+        if args.full and world == 1 and not use_dist and not args.no_reference_protocol and code == 0:
             big = nnz > 200e6
             rp = reference_protocol(args, fmt, 10 if big else 20)
             if rp is not None:

@@ -575,7 +575,7 @@ def test_multi_gpu_context_coo_and_ellpack_blocks(oracle, fmt, parts, balance):
 def test_bench_on_a_matrix_market_file(tmp_path):
     """bench.py --matrix FILE: what a box that has the SuiteSparse files runs.  A symmetric file (the 1138_bus
     stand-in) packed the way SuiteSparse ships (NAME.tar.gz holding NAME/NAME.mtx), stored triangle only and with
-    --expand-symmetric, CSR and COO: one JSON line each, named after the file, parity against the CPU kernel."""
+    --expand-symmetric, CSR and COO: one JSON line each, named after the file, parity against the CPU kernel (--full)."""
     import json
     import shutil
     import subprocess
@@ -592,7 +592,7 @@ def test_bench_on_a_matrix_market_file(tmp_path):
     stored = None
     for extra, fmt in (([], "csr"), (["--expand-symmetric"], "csr"), (["--expand-symmetric"], "coo")):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--matrix", str(archive), "--format", fmt, "--steps", "3",
-                            "--warmup", "1", "--cpu-seconds", "0.2", "--no-reference-protocol"] + extra,
+                            "--warmup", "1", "--full", "--cpu-seconds", "0.2", "--no-reference-protocol"] + extra,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,10 +1,12 @@
 #!/bin/bash
 # tools/bench_all.sh TAG -- on the GPU box: bench.py over every BASELINE configuration and format
-# (non-profiled; each line carries roofline + cpu_baseline + parity); lines go to gpurun_out/TAG_*.log
+# (non-profiled, --full: each line carries roofline + cpu_baseline + parity); lines go to $OUT/TAG_*.log (BENCH_OUT, default bench_out)
 TAG=${1:-bench}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
-run() { name=$1; shift; python3 bench.py --steps 50 --warmup 10 --cpu-seconds 4 --no-companions --no-config3 --no-drop-in ${LIVE_PMC:---no-live-pmc} "$@" > gpurun_out/${TAG}_$name.log 2> gpurun_out/${TAG}_$name.err || { echo "$name FAILED"; tail -3 gpurun_out/${TAG}_$name.err; }; python3 - gpurun_out/${TAG}_$name.log $name <<'PY'
+OUT=${BENCH_OUT:-bench_out}
+mkdir -p "$OUT"
+run() { name=$1; shift; python3 bench.py --full --steps 50 --warmup 10 --cpu-seconds 4 --no-companions --no-config3 --no-drop-in ${LIVE_PMC:---no-live-pmc} "$@" > "$OUT/${TAG}_$name.log" 2> "$OUT/${TAG}_$name.err" || { echo "$name FAILED"; tail -3 "$OUT/${TAG}_$name.err"; }; python3 - "$OUT/${TAG}_$name.log" $name <<'PY'
 import json, sys
 try:
     d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -53,7 +55,7 @@ run poisson3d_csr --matrix synthetic:poisson3d:256
 # the launches of tests/test_gpu_perf_floor.py measured on this box -- measured and logged only: updating the committed table
 # (tests/golden/perf_floor.json) is an explicit, reviewed step (python3 tools/perf_floor.py --write), never a side effect of a
 # sweep, or a regressed build run through this script would loosen the very floor that exists to catch it
-python3 tools/perf_floor.py > gpurun_out/${TAG}_perf_floor.log 2>&1
+python3 tools/perf_floor.py > "$OUT/${TAG}_perf_floor.log" 2>&1
 # the SuiteSparse files themselves, where a box has them (same switch as tests/test_gpu_realfiles.py)
 if [ -n "$SPMV_SUITESPARSE_DIR" ]; then
   for name in 1138_bus Queen_4147 nlpkkt200 webbase-1M; do

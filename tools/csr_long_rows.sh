@@ -4,12 +4,14 @@
 cd ${GRAFT_REPO_ROOT:-.}
 SPECS=${SPECS:-"400000,300 400000,400 400000,500 400000,750 200000,1000 100000,1024 100000,1500 50000,2000 25000,4095"}
 FLAGS=${FLAGS:-"0 0x8000000"}
+TMP=$(mktemp -d)
+trap 'rm -rf "$TMP"' EXIT
 for spec in $SPECS; do
   for flags in $FLAGS; do
-  python3 bench.py --matrix synthetic:banded:$spec --format csr --flags $flags --steps 10 --warmup 3 --no-cpu-baseline --no-reference-protocol > gpurun_out/csr_tmp.log 2> gpurun_out/csr_tmp.err || { echo FAILED; tail -3 gpurun_out/csr_tmp.err; }
-  python3 - $spec $flags <<'PY'
+  python3 bench.py --matrix synthetic:banded:$spec --format csr --flags $flags --steps 10 --warmup 3 --full --no-cpu-baseline --no-reference-protocol > "$TMP/csr.log" 2> "$TMP/csr.err" || { echo FAILED; tail -3 "$TMP/csr.err"; }
+  python3 - $spec $flags "$TMP/csr.log" <<'PY'
 import json, sys
-d = json.loads([l for l in open("gpurun_out/csr_tmp.log") if l.startswith("{")][-1])
+d = json.loads([l for l in open(sys.argv[3]) if l.startswith("{")][-1])
 r = d["roofline"]
 print("banded %s csr flags %s: %.1f us frac %.3f streamed/triad %.3f tiles=%s" % (sys.argv[1], sys.argv[2], r["kernel_us"], r["frac"], r["streamed"]["frac_of_triad"], d["config"].get("tiles")))
 PY

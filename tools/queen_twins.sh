@@ -4,12 +4,14 @@
 cd ${GRAFT_REPO_ROOT:-.}
 SPECS=${SPECS:-"110,71,177 110,71,177,3,20 110,71,177,3,100 110,71,177,3,0,1000 110,71,177,3,20,1000 110,71,177,6 110,71,177,6,20"}
 FLAGS=${FLAGS:-"0 0x20000000 0x2000000"}
+TMP=$(mktemp -d)
+trap 'rm -rf "$TMP"' EXIT
 for spec in $SPECS; do
   for flags in $FLAGS; do
-  python3 bench.py --matrix synthetic:queen:$spec --flags $flags --steps 30 --warmup 5 --no-cpu-baseline --no-reference-protocol --no-cold > gpurun_out/queen_tmp.log 2> gpurun_out/queen_tmp.err || { echo FAILED; tail -3 gpurun_out/queen_tmp.err; }
-  python3 - $spec $flags <<'PY'
+  python3 bench.py --matrix synthetic:queen:$spec --flags $flags --steps 30 --warmup 5 --full --no-cpu-baseline --no-reference-protocol --no-cold > "$TMP/queen.log" 2> "$TMP/queen.err" || { echo FAILED; tail -3 "$TMP/queen.err"; }
+  python3 - $spec $flags "$TMP/queen.log" <<'PY'
 import json, sys
-d = json.loads([l for l in open("gpurun_out/queen_tmp.log") if l.startswith("{")][-1])
+d = json.loads([l for l in open(sys.argv[3]) if l.startswith("{")][-1])
 r = d["roofline"]
 pm = r.get("plan_ms") or {}
 print("queen %-24s flags %-10s %7.1f us  frac(8d) %.3f  streamed/triad %.3f  plan %.1f ms  parity %s  tiles=%s" % (
