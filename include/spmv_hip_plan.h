@@ -142,7 +142,8 @@ void spmv_hip_plan_destroy(spmv_hip_plan *plan);
  *             spmv_hip_plan_csr_repack; never with SPMV_HIP_FLAG_NO_BLOCK_TILES or a value dictionary)  [36] their entries
  *        [37] the rows per group of those tiles (0 = none)
  *        [38] chunks of stencil row runs (up to 128 rows each; 0 = none, see SPMV_HIP_FLAG_NO_STENCIL_RUNS)  [39] tiles merged
- *             into those runs  [40] their entries */
+ *             into those runs  [40] their entries  [41] chunks among [38] that hold a row with missing positions (row masks)
+ *        [42] tiles left to a second launch beside the runs (0 with runs: one launch) */
 int spmv_hip_plan_info(const spmv_hip_plan *plan, int64_t *out, int n);
 
 /* y += A*x, CSR.  Replaces csr_spmv / csr_spmv_inner_loop

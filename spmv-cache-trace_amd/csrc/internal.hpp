@@ -115,12 +115,16 @@ struct spmv_hip_plan {
     int blockwin_tiles = 0;
     int32_t * d_rest_tiles = nullptr; // with block / segment windows: the tiles NOT marked for them (what csr_wavetile_kernel<LIST> multiplies)
     int nrest_tiles = 0;
-    // stencil row runs (csr_runs.hpp): chunks of up to 128 rows of runs of stencil-row tiles that share a row length and a
-    // pattern record, multiplied by csr_wavetile_kernel_runs; every other tile is in d_run_rest (csr_wavetile_kernel<LIST>)
-    int4 * d_run_chunks = nullptr; // {first row, first entry, rows, pattern}
+    // stencil row runs (csr_runs.hpp): chunks of up to 128 rows whose rows follow one 5-entry pattern fully or as a subset,
+    // multiplied by csr_runs_kernel; every other tile is in d_run_rest (csr_wavetile_kernel<LIST>)
+    int4 * d_run_chunks = nullptr; // {first row, first entry, rows | entries << 8, mask slot or -1}
+    uint8_t * d_run_masks = nullptr; // 128 row masks per masked chunk
     int32_t * d_run_rest = nullptr;
-    int nrun_chunks = 0, nrun_rest = 0, run_len = 0, run_tiles = 0;
+    int nrun_chunks = 0, nrun_rest = 0, run_len = 0, run_tiles = 0, run_masked_chunks = 0;
     long long run_entries = 0;
+    spmv::RunPattern run_pattern{};
+    bool run_dense = false; // chunk c is rows [128 c, 128 c + 128): the kernel issues x and y_in before its descriptor returns
+    bool run_nt = false;    // the value loads carry `nt`
     // row-group plans (csr_rowgroup.hpp): the tiles csr_rowgroup_kernel multiplies, and the others (csr_wavetile_kernel<LIST>)
     int32_t * d_group_tiles = nullptr, * d_group_rest = nullptr;
     int ngroup_tiles = 0, ngroup_rest = 0;

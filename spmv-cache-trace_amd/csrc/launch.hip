@@ -249,9 +249,12 @@ static int csr_spmv_launch(const spmv_hip_plan * pl, const int32_t * p, const in
 #endif
             ) {
                 // stencil row runs (csr_runs.hpp): a wave per chunk of 128 rows (a grid of resident waves that walk the chunks measured
-                // 212 against 188 us on Poisson 4096^2; a wave per chunk 180), then the other tiles
+                // 212 against 188 us on Poisson 4096^2; a wave per chunk 180), then the other tiles, if any
                 const dim3 grid((unsigned) ((pl->nrun_chunks + spmv::kRunWaves - 1) / spmv::kRunWaves));
-                hipLaunchKernelGGL((spmv::csr_wavetile_kernel_runs<5>), grid, dim3(256), 0, s, pl->nrun_chunks, pl->d_run_chunks, pl->d_patterns, a, x, y_in, y);
+                auto runs = pl->run_dense ? (pl->run_nt ? spmv::csr_runs_kernel<true, true> : spmv::csr_runs_kernel<true, false>)
+                                          : (pl->run_nt ? spmv::csr_runs_kernel<false, true> : spmv::csr_runs_kernel<false, false>);
+                hipLaunchKernelGGL(runs, grid, dim3(256), 0, s, pl->nrun_chunks, pl->rows, pl->cols, pl->d_run_chunks, pl->d_run_masks,
+                                   pl->run_pattern, a, x, y_in, y);
                 if (pl->nrun_rest > 0)
                     hipLaunchKernelGGL((spmv::csr_wavetile_kernel<512, true, true, false, 0, 0, false, false, false, true>), dim3((unsigned) ((pl->nrun_rest + 3) / 4)),
                                        dim3(256), 0, s, pl->nrun_rest, pl->d_tiles, p, j, pl->d_col16, a, x, y_in, y, pl->nnz, pl->cols, exact, pl->d_patterns,

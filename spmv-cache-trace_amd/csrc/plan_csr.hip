@@ -135,24 +135,38 @@ int verify_plan(const spmv_hip_plan * pl, const int32_t * d_column_index, hipStr
     return SPMV_HIP_OK;
 }
 
+// Plan time: out[i] = j16[idx[i]] (the row masks that masked stencil tiles keep in their 16-bit column slots)
+static __global__ void run_gather_u16(const uint16_t * __restrict__ j16, const int32_t * __restrict__ idx, uint16_t * __restrict__ out, int n)
+{
+    const int i = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n)
+        out[i] = j16[idx[i]];
+}
+
 void drop_stencil_runs(spmv_hip_plan * pl)
 {
-    for (void * q : {(void *) pl->d_run_chunks, (void *) pl->d_run_rest})
+    for (void * q : {(void *) pl->d_run_chunks, (void *) pl->d_run_rest, (void *) pl->d_run_masks})
         if (q)
             (void) hipFree(q);
     pl->d_run_chunks = nullptr;
     pl->d_run_rest = nullptr;
-    pl->nrun_chunks = pl->nrun_rest = pl->run_len = pl->run_tiles = 0;
+    pl->d_run_masks = nullptr;
+    pl->nrun_chunks = pl->nrun_rest = pl->run_len = pl->run_tiles = pl->run_masked_chunks = 0;
     pl->run_entries = 0;
+    pl->run_dense = pl->run_nt = false;
 }
 
 // Stencil row runs (csr_runs.hpp).  Only for the launch that would otherwise multiply every tile with the plain default
 // kernel (launch.hip checks the launch-time half: 16-bit stream of this column array, no dictionary in use, no panels, no
-// peers, 16-byte aligned values).  A tile joins a run when the default kernel would take its `stencil_values` path: a fast
-// stream tile, shifted, uniform, one lane per row, its rows of L = 5 entries, columns from a pattern record, no
-// other class on top; a run is a maximal sequence of such tiles with the same L and pattern record (contiguous rows and
-// entries by construction).  Runs are cut into chunks of 128 rows (never one of a single row); the other tiles keep their
-// descriptors and go to the rest list.  Nothing changes what a multiply streams: plan_account's numbers stay as they are.
+// peers, 16-byte aligned values).  The run pattern P is the pattern record of most entries among the tiles the default kernel
+// takes down its `stencil_values` path with rows of 5 entries (a fast stream tile, shifted, uniform, one lane per row, columns
+// from a pattern record, no other class on top).  A tile joins the chunks when every row's columns are a subset of
+// {row + P[p]} and the default kernel adds them left to right as the run kernel does: such a stencil_values tile of up to 5
+// entries per row whose record is a sub-pattern of P (the first and last grid lines), or a masked stencil tile whose rows'
+// positions all lie in P (the line-end / line-start pairs, the corners).  Ranges of consecutive such tiles are cut at absolute
+// multiples of 128 rows (a range edge elsewhere moves a cut by a row rather than leave a chunk of one row); a chunk that holds a
+// row with missing positions gets 128 row masks in a side array.  The other tiles keep their descriptors and go to the rest list.
+// Nothing changes what a multiply streams: plan_account's numbers stay as they are.
 static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, bool compressed)
 {
     drop_stencil_runs(pl);
@@ -161,64 +175,251 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
         && 2 * (long long) pl->xwin_tiles > pl->ntiles;
     if ((pl->flags & (SPMV_HIP_FLAG_NO_STENCIL_RUNS | SPMV_HIP_FLAG_XCD_REMAP)) || !compressed || pl->nvalues > 0 || pl->balanced
         || pl->inner || pl->d_blocks || pl->d_segblocks || pl->tile != 512 || pl->npatterns == 0 || pl->cols >= (1 << 29) || xwin_launch
-        || pl->algorithm != SPMV_HIP_CSR_WAVETILE || pl->ntiles == 0)
+        || pl->algorithm != SPMV_HIP_CSR_WAVETILE || pl->ntiles == 0 || pl->cols < 2)
         return SPMV_HIP_OK;
+    // plan-time switches of the experiments build (tools/ab.py): chunks cut from each range's first row instead of at multiples of
+    // 128, no rows with missing positions in chunks, x / y_in loads issued before the descriptor returns (off by default: it
+    // measured no faster), value loads without `nt`
+    bool align = true, masked = true, early = false, nt = true;
+#ifdef SPMV_HIP_EXPERIMENTS
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_ALIGN")) align = std::atoi(v) != 0;
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_MASKED")) masked = std::atoi(v) != 0;
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_EARLY")) early = std::atoi(v) != 0;
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_NT")) nt = std::atoi(v) != 0;
+#endif
+    constexpr int L = spmv::kRunLen;
     const int ntiles = pl->ntiles;
-    auto run_len = [&](int w) -> int { // L if tile w belongs in a run, else 0
+    // a tile the default kernel multiplies with `stencil_values` (its rows left to right, one lane each): its row length, else 0
+    auto values_len = [&](int w) -> int {
         const int4 t = d[(size_t) w];
         const int meta = t.z;
         const int k0 = t.y, k1 = d[(size_t) w + 1].y;
-        const int L = meta & 0xFFFF;
         const int need = spmv::kTileMetaFast | spmv::kTileMetaShifted | spmv::kTileMetaUniform | spmv::kTileMetaPattern;
         if ((t.x & spmv::kTileFlagPartial) || k1 <= k0 || (meta & need) != need || ((meta >> spmv::kTileMetaLanesShift) & 7) != 0
             || (meta & (spmv::kTileMetaBlockWin | spmv::kTileMetaBlock3)) || spmv::is_masked_stencil_tile(meta) || k1 - (k0 & ~3) > 512)
             return 0;
-        return L == 5 ? L : 0; // (7-point rows were measured slower: 250 against 240 us on a 256^3 grid)
+        return meta & 0xFFFF;
     };
-    constexpr int L = 5;
-    long long run_candidates = 0;
+    // a plain tile of 16-bit column offsets whose rows of up to 5 entries the default kernel adds one lane per row, left to right
+    // (tile_row_sum<1>; uniform: no padding): the rows a grid line's boundary leaves in tiles of their own
+    auto narrow_tile = [&](int w) -> bool {
+        const int4 t = d[(size_t) w];
+        const int meta = t.z;
+        const int k0 = t.y, k1 = d[(size_t) w + 1].y;
+        const int need = spmv::kTileMetaFast | spmv::kTileMetaNarrow | spmv::kTileMetaUniform;
+        const int nrows = (d[(size_t) w + 1].x & ~spmv::kTileFlagPartial) - t.x;
+        return !(t.x & spmv::kTileFlagPartial) && k1 > k0 && (meta & need) == need && ((meta >> spmv::kTileMetaLanesShift) & 7) == 0
+            && !(meta & (spmv::kTileMetaShifted | spmv::kTileMetaPattern | spmv::kTileMetaBlockWin | spmv::kTileMetaBlock3))
+            && (meta & 0xFFFF) >= 1 && (meta & 0xFFFF) <= L && nrows >= 1 && nrows <= spmv::kRunChunkRows
+            && (long long) nrows * (meta & 0xFFFF) == (long long) (k1 - k0) && k1 - (k0 & ~3) <= 512;
+    };
+    auto masked_tile = [&](int w) -> bool {
+        const int4 t = d[(size_t) w];
+        return !(t.x & spmv::kTileFlagPartial) && d[(size_t) w + 1].y > t.y && (t.z & spmv::kTileMetaFast) && spmv::is_masked_stencil_tile(t.z)
+            && !(t.z & (spmv::kTileMetaBlockWin | spmv::kTileMetaBlock3));
+    };
+    // P: the record of most entries in rows of 5 (7-point rows were measured slower: 250 against 240 us on a 256^3 grid)
+    std::vector<long long> per_pattern((size_t) pl->npatterns, 0);
     for (int w = 0; w < ntiles; ++w)
-        if (run_len(w))
-            run_candidates += (long long) d[(size_t) w + 1].y - d[(size_t) w].y;
-    if (2 * run_candidates <= (long long) pl->nnz)
+        if (values_len(w) == L && d[(size_t) w].w >= 0 && d[(size_t) w].w < pl->npatterns)
+            per_pattern[(size_t) d[(size_t) w].w] += (long long) d[(size_t) w + 1].y - d[(size_t) w].y;
+    const int P = (int) (std::max_element(per_pattern.begin(), per_pattern.end()) - per_pattern.begin());
+    if (2 * per_pattern[(size_t) P] <= (long long) pl->nnz)
         return SPMV_HIP_OK; // runs pay only where they cover most of the matrix
-    std::vector<int4> chunks;
+    std::vector<int32_t> recs((size_t) pl->npatterns * spmv::kPatStride);
+    HIP_TRY(hipMemcpy(recs.data(), pl->d_patterns, recs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    spmv::RunPattern rp{};
+    for (int q = 0; q < L; ++q)
+        rp.rel[q] = recs[(size_t) P * spmv::kPatStride + spmv::kPatRel + q];
+    // position bits of a record in P's positions (bit q of the result: P[q]), -1 where a position is not in P
+    std::vector<std::vector<int>> map((size_t) pl->npatterns);
+    for (int r = 0; r < pl->npatterns; ++r) {
+        const int32_t * rec = &recs[(size_t) r * spmv::kPatStride];
+        const int len = rec[0];
+        for (int i = 0, q = 0; i < len && i < spmv::kStencilMaskMaxLen; ++i) {
+            while (q < L && rp.rel[q] < rec[spmv::kPatRel + i])
+                ++q;
+            map[(size_t) r].push_back(q < L && rp.rel[q] == rec[spmv::kPatRel + i] ? q++ : -1);
+        }
+    }
+    auto in_p = [&](int rec, unsigned m, unsigned & out) -> bool { // a record's position mask in P's positions
+        if (rec < 0 || rec >= pl->npatterns)
+            return false;
+        const std::vector<int> & mp = map[(size_t) rec];
+        out = 0;
+        for (int i = 0; i < 16 && (m >> i); ++i)
+            if ((m >> i) & 1u) {
+                if (i >= (int) mp.size() || mp[(size_t) i] < 0)
+                    return false;
+                out |= 1u << mp[(size_t) i];
+            }
+        return true;
+    };
+    // the masked stencil tiles' row masks (16-bit column slots k0 + row) and the plain narrow tiles' column offsets (slots k0 ... k1),
+    // gathered on the device
+    std::vector<uint16_t> tmask;
+    std::vector<long long> tmask_at((size_t) ntiles, -1);
+    if (masked) {
+        std::vector<int32_t> idx;
+        for (int w = 0; w < ntiles; ++w)
+            if (masked_tile(w)) {
+                tmask_at[(size_t) w] = (long long) idx.size();
+                const int r0 = d[(size_t) w].x, r1 = d[(size_t) w + 1].x & ~spmv::kTileFlagPartial;
+                for (int r = r0; r < r1; ++r)
+                    idx.push_back(d[(size_t) w].y + (r - r0));
+            } else if (narrow_tile(w)) {
+                tmask_at[(size_t) w] = (long long) idx.size();
+                for (int k = d[(size_t) w].y; k < d[(size_t) w + 1].y; ++k)
+                    idx.push_back(k);
+            }
+        if (!idx.empty() && pl->d_col16) {
+            int32_t * d_idx = nullptr;
+            uint16_t * d_out = nullptr;
+            hipError_t e = hipMalloc((void **) &d_idx, idx.size() * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMalloc((void **) &d_out, idx.size() * sizeof(uint16_t));
+            if (e == hipSuccess) e = hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(run_gather_u16, dim3((unsigned) ((idx.size() + 255) / 256)), dim3(256), 0, 0,
+                                   (const uint16_t *) pl->d_col16, d_idx, d_out, (int) idx.size());
+                e = hipGetLastError();
+            }
+            tmask.resize(idx.size());
+            if (e == hipSuccess) e = hipMemcpy(tmask.data(), d_out, tmask.size() * sizeof(uint16_t), hipMemcpyDeviceToHost);
+            (void) hipFree(d_idx);
+            (void) hipFree(d_out);
+            HIP_TRY(e);
+        } else {
+            std::fill(tmask_at.begin(), tmask_at.end(), -1);
+        }
+    }
+    // per row of a taken tile: its mask in P's positions (0: the row is not in a chunk)
+    std::vector<uint8_t> rmask((size_t) pl->rows, 0);
     std::vector<int32_t> rest;
     long long entries = 0;
     int tiles = 0;
-    for (int w = 0; w < ntiles;) {
-        if (run_len(w) != L) {
-            rest.push_back(w++);
+    for (int w = 0; w < ntiles; ++w) {
+        const int r0 = d[(size_t) w].x & ~spmv::kTileFlagPartial, r1 = d[(size_t) w + 1].x & ~spmv::kTileFlagPartial;
+        const int k0 = d[(size_t) w].y, k1 = d[(size_t) w + 1].y;
+        bool take = false;
+        const int len = values_len(w);
+        unsigned m = 0;
+        if (len > 0 && len <= L && in_p(d[(size_t) w].w, (1u << len) - 1u, m) && (masked || m == (1u << L) - 1u)
+            && (long long) (r1 - r0) * len == (long long) (k1 - k0)) {
+            take = true;
+            for (int r = r0; r < r1; ++r)
+                rmask[(size_t) r] = (uint8_t) m;
+        } else if (tmask_at[(size_t) w] >= 0 && narrow_tile(w)) {
+            // columns d.w + offset, ascending: each must be row + P[q] for a later q than the one before
+            const int rl = d[(size_t) w].z & 0xFFFF;
+            take = true;
+            for (int r = r0; r < r1 && take; ++r) {
+                unsigned rm = 0;
+                for (int i = 0, q = 0; i < rl && take; ++i) {
+                    const long long rel = (long long) d[(size_t) w].w + tmask[(size_t) (tmask_at[(size_t) w] + (long long) (r - r0) * rl + i)] - r;
+                    while (q < L && rp.rel[q] < rel)
+                        ++q;
+                    take = q < L && rp.rel[q] == rel;
+                    rm |= take ? 1u << q++ : 0u;
+                }
+                rmask[(size_t) r] = (uint8_t) rm;
+            }
+            if (!take)
+                std::fill(rmask.begin() + r0, rmask.begin() + r1, (uint8_t) 0);
+        } else if (tmask_at[(size_t) w] >= 0) {
+            take = true;
+            long long k = 0;
+            for (int r = r0; r < r1 && take; ++r) {
+                const unsigned tm = tmask[(size_t) (tmask_at[(size_t) w] + (r - r0))];
+                take = tm != 0 && in_p(d[(size_t) w].w, tm, m);
+                rmask[(size_t) r] = (uint8_t) m;
+                k += __builtin_popcount(m);
+            }
+            take = take && k == (long long) (k1 - k0);
+            if (!take)
+                std::fill(rmask.begin() + r0, rmask.begin() + r1, (uint8_t) 0);
+        }
+        if (take) {
+            entries += (long long) k1 - k0;
+            ++tiles;
+        } else {
+            rest.push_back(w);
+        }
+    }
+    if (2 * entries <= (long long) pl->nnz)
+        return SPMV_HIP_OK;
+    // ranges of consecutive taken rows, cut at multiples of 128 rows
+    std::vector<int4> chunks;
+    std::vector<uint8_t> cmasks;
+    const unsigned full = (1u << L) - 1u;
+    auto add_chunk = [&](int r, int n, int e) {
+        int k = 0;
+        bool all = true;
+        for (int i = 0; i < n; ++i) {
+            k += __builtin_popcount(rmask[(size_t) r + i]);
+            all = all && rmask[(size_t) r + i] == full;
+        }
+        int slot = -1;
+        if (!all) {
+            slot = (int) (cmasks.size() / spmv::kRunChunkRows);
+            cmasks.resize(cmasks.size() + spmv::kRunChunkRows, 0);
+            std::copy(rmask.begin() + r, rmask.begin() + r + n, cmasks.begin() + (size_t) slot * spmv::kRunChunkRows);
+        }
+        chunks.push_back(int4{r, e, n | (k << 8), slot});
+        return k;
+    };
+    // the first entry of every row range: the taken tiles' first entries
+    int e = 0;
+    for (int w = 0, r = 0; w < ntiles; ++w) {
+        const int r0 = d[(size_t) w].x & ~spmv::kTileFlagPartial, r1 = d[(size_t) w + 1].x & ~spmv::kTileFlagPartial;
+        if (r1 <= r0 || rmask[(size_t) r0] == 0 || r0 < r)
+            continue;
+        // a range starts at r0 and takes every following taken tile
+        int q = w + 1;
+        while (q < ntiles && (d[(size_t) q + 1].x & ~spmv::kTileFlagPartial) > (d[(size_t) q].x & ~spmv::kTileFlagPartial)
+               && rmask[(size_t) (d[(size_t) q].x & ~spmv::kTileFlagPartial)] != 0)
+            ++q;
+        const int end = d[(size_t) q].x & ~spmv::kTileFlagPartial;
+        e = d[(size_t) w].y;
+        if (end - r0 < 2) { // a range of one row: its tile stays with the rest list
+            for (int t = w; t < q; ++t) {
+                rest.push_back(t);
+                entries -= (long long) d[(size_t) t + 1].y - d[(size_t) t].y;
+                --tiles;
+            }
+            std::fill(rmask.begin() + r0, rmask.begin() + end, (uint8_t) 0);
+            r = end;
+            w = q - 1;
             continue;
         }
-        const int pat = d[(size_t) w].w;
-        int e = w + 1;
-        while (e < ntiles && run_len(e) == L && d[(size_t) e].w == pat)
-            ++e;
-        const int r0 = d[(size_t) w].x, r1 = d[(size_t) e].x & ~spmv::kTileFlagPartial;
-        const int k0 = d[(size_t) w].y;
-        if (r1 - r0 < 2) {
-            for (int q = w; q < e; ++q)
-                rest.push_back(q);
-        } else {
-            for (int r = r0; r < r1;) {
-                int n = std::min(spmv::kRunChunkRows, r1 - r);
-                if (r1 - r - n == 1)
-                    --n; // no chunk of one row: 127 + 2
-                chunks.push_back(int4{r, k0 + (r - r0) * L, n, pat});
-                r += n;
-            }
-            entries += (long long) d[(size_t) e].y - k0;
-            tiles += e - w;
+        for (int c = r0; c < end;) { // (end - c >= 2 throughout)
+            int stop = align ? std::min(end, (c / spmv::kRunChunkRows + 1) * spmv::kRunChunkRows) : std::min(end, c + spmv::kRunChunkRows);
+            if (stop - c == 1)
+                ++stop; // no chunk of one row at a range's start: 2 + 127
+            if (end - stop == 1)
+                stop = stop - c < spmv::kRunChunkRows ? end : stop - 1; // ... nor at its end: 127 + 2
+            e += add_chunk(c, stop - c, e);
+            c = stop;
         }
-        w = e;
+        if (e != d[(size_t) q].y)
+            return SPMV_HIP_OK; // (cannot happen: the taken rows' masks count the range's entries)
+        r = end;
+        w = q - 1;
     }
-    if (chunks.empty())
+    if (chunks.empty() || 2 * entries <= (long long) pl->nnz)
         return SPMV_HIP_OK;
+    std::sort(rest.begin(), rest.end());
+    bool dense = early && (long long) chunks.size() == ((long long) pl->rows + spmv::kRunChunkRows - 1) / spmv::kRunChunkRows;
+    for (size_t c = 0; c < chunks.size() && dense; ++c)
+        dense = chunks[c].x == (int) c * spmv::kRunChunkRows && (chunks[c].z & 0xFF) == std::min(spmv::kRunChunkRows, pl->rows - chunks[c].x);
     HIP_TRY(hipMalloc((void **) &pl->d_run_chunks, chunks.size() * sizeof(int4)));
     HIP_TRY(hipMemcpy(pl->d_run_chunks, chunks.data(), chunks.size() * sizeof(int4), hipMemcpyHostToDevice));
+    if (!cmasks.empty()) {
+        HIP_TRY(hipMalloc((void **) &pl->d_run_masks, cmasks.size()));
+        HIP_TRY(hipMemcpy(pl->d_run_masks, cmasks.data(), cmasks.size(), hipMemcpyHostToDevice));
+    }
     pl->nrun_chunks = (int) chunks.size();
     pl->nrun_rest = (int) rest.size();
+    pl->run_masked_chunks = (int) (cmasks.size() / spmv::kRunChunkRows);
     if (!rest.empty()) {
         rest.resize((rest.size() + 3) & ~(size_t) 3, rest.back()); // padded to whole workgroups (never read past nrun_rest)
         HIP_TRY(hipMalloc((void **) &pl->d_run_rest, rest.size() * sizeof(int32_t)));
@@ -227,6 +428,9 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
     pl->run_len = L;
     pl->run_tiles = tiles;
     pl->run_entries = entries;
+    pl->run_pattern = rp;
+    pl->run_dense = dense;
+    pl->run_nt = nt;
     return SPMV_HIP_OK;
 }
 
@@ -2204,7 +2408,7 @@ int spmv_hip_plan_info(const spmv_hip_plan * pl, int64_t * out, int n)
 {
     if (!pl || !out || n < 0)
         return fail(SPMV_HIP_ERR_INVALID, "plan/out null");
-    const int64_t v[41] = {pl->algorithm, pl->lanes_per_row, pl->workgroups, pl->nblk,
+    const int64_t v[43] = {pl->algorithm, pl->lanes_per_row, pl->workgroups, pl->nblk,
                            pl->long_blocks, pl->rows, pl->nnz, (int64_t) pl->meta_bytes, pl->narrow_tiles,
                            pl->uniform_tiles, pl->shifted_tiles, pl->xwin_tiles, pl->blockwin_tiles,
                            pl->inner ? pl->inner->ntiles : 0, pl->streamed_bytes, pl->shifted_entries,
@@ -2215,8 +2419,9 @@ int spmv_hip_plan_info(const spmv_hip_plan * pl, int64_t * out, int n)
                            pl->ngroup_tiles, pl->nvalues > 0 ? 0 : pl->masked_block_tiles, pl->nvalues > 0 ? 0 : pl->masked_block_entries,
                            pl->stencil_mask_tiles, pl->stencil_mask_entries,
                            pl->nvalues > 0 ? 0 : pl->colshare_tiles, pl->nvalues > 0 ? 0 : pl->colshare_entries,
-                           pl->colshare_tiles > 0 ? pl->block_hint : 0, pl->nrun_chunks, pl->run_tiles, pl->run_entries};
-    for (int i = 0; i < n && i < 41; ++i)
+                           pl->colshare_tiles > 0 ? pl->block_hint : 0, pl->nrun_chunks, pl->run_tiles, pl->run_entries,
+                           pl->run_masked_chunks, pl->nrun_chunks > 0 ? pl->nrun_rest : 0};
+    for (int i = 0; i < n && i < 43; ++i)
         out[i] = v[i];
     return SPMV_HIP_OK;
 }
