@@ -123,7 +123,7 @@ struct spmv_hip_plan {
     int nrun_chunks = 0, nrun_rest = 0, run_len = 0, run_tiles = 0, run_masked_chunks = 0;
     long long run_entries = 0;
     spmv::RunPattern run_pattern{};
-    bool run_dense = false; // chunk c is rows [128 c, 128 c + 128): the kernel issues x and y_in before its descriptor returns
+    bool run_dense = false; // chunk c is rows [128 c, 128 c + 128): the kernel takes the rows from the chunk number
     bool run_nt = false;    // the value loads carry `nt`
     // row-group plans (csr_rowgroup.hpp): the tiles csr_rowgroup_kernel multiplies, and the others (csr_wavetile_kernel<LIST>)
     int32_t * d_group_tiles = nullptr, * d_group_rest = nullptr;

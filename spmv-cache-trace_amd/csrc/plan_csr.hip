@@ -178,8 +178,8 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
         || pl->algorithm != SPMV_HIP_CSR_WAVETILE || pl->ntiles == 0 || pl->cols < 2)
         return SPMV_HIP_OK;
     // plan-time switches of the experiments build (tools/ab.py): chunks cut from each range's first row instead of at multiples of
-    // 128, no rows with missing positions in chunks, x / y_in loads issued before the descriptor returns (off by default: it
-    // measured no faster), value loads without `nt`
+    // 128, no rows with missing positions in chunks, rows taken from the chunk number where the chunks are dense (off by default:
+    // it measured no faster), value loads without `nt`
     bool align = true, masked = true, early = false, nt = true;
 #ifdef SPMV_HIP_EXPERIMENTS
     if (const char * v = std::getenv("SPMV_HIP_RUNS_ALIGN")) align = std::atoi(v) != 0;
