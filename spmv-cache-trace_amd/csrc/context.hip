@@ -21,6 +21,10 @@ void free_ctx_matrix(spmv_hip_ctx * c)
         spmv_hip_sym_plan_destroy(c->sym_plan);
         c->sym_plan = nullptr;
     }
+    if (c->tr_plan) {
+        spmv_hip_tr_plan_destroy(c->tr_plan);
+        c->tr_plan = nullptr;
+    }
     if (c->mv_plan) {
         spmv_hip_mv_plan_destroy(c->mv_plan);
         c->mv_plan = nullptr;
@@ -741,6 +745,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
     switch (c->format) {
     case 1: rc = csr_run(); break;
     case 5: rc = spmv_hip_csr_symv(c->sym_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
+    case 6: rc = spmv_hip_csr_spmv_t(c->tr_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
     case 2:
         rc = c->as_csr ? csr_run() : ctx_coo_run(c, c->nnz, c->d_idx, c->d_col, c->d_val);
         break;
@@ -877,6 +882,12 @@ int spmv_hip_ctx_info(spmv_hip_ctx * c, int64_t * out, int n)
         spmv_hip_sym_plan_info(c->sym_plan, si, 14);
         v[6] = si[0];
         v[15] = si[13];
+    }
+    if (c->tr_plan) { // format 6: workgroups = ranges, streamed bytes of the matrix as stored
+        int64_t ti[SPMV_HIP_TR_INFO] = {0};
+        spmv_hip_tr_plan_info(c->tr_plan, ti, SPMV_HIP_TR_INFO);
+        v[6] = ti[0];
+        v[15] = ti[11];
     }
     if (c->d_prow)
         v[14] += c->coo_panel_blocks; // COO (part) in column panels: workgroups per panel

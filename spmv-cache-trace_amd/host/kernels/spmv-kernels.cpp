@@ -7,6 +7,7 @@
 
 #include "spmv_hip_symmetric.h" // (spmv_hip_plan.h, spmv_hip_tuning.h, spmv_hip.h)
 #include "spmv_hip_multivec.h"
+#include "spmv_hip_transpose.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -60,9 +61,31 @@ csr_matrix::Matrix load_csr(std::string const & path, SpmvOptions const & opt, s
     return csr_matrix::from_matrix_market(load(path, opt, o, verbose));
 }
 
+// A' as a CSR matrix of its own: a stable counting sort by column, so every column's entries stay in ascending row order
+csr_matrix::Matrix transposed_on_host(csr_matrix::Matrix const & A)
+{
+    std::size_t const nnz = (std::size_t) A.row_ptr[(std::size_t) A.rows];
+    csr_matrix::size_array_type p((std::size_t) A.columns + 1, 0);
+    for (std::size_t e = 0; e < nnz; ++e)
+        ++p[(std::size_t) A.column_index[e] + 1];
+    for (std::size_t j = 0; j < (std::size_t) A.columns; ++j)
+        p[j + 1] += p[j];
+    std::vector<csr_matrix::size_type> next(p.begin(), p.end() - 1);
+    csr_matrix::index_array_type c(nnz, 0);
+    csr_matrix::value_array_type v(nnz, 0.0);
+    for (csr_matrix::index_type r = 0; r < A.rows; ++r)
+        for (csr_matrix::size_type e = A.row_ptr[(std::size_t) r]; e < A.row_ptr[(std::size_t) r + 1]; ++e) {
+            std::size_t const k = (std::size_t) next[(std::size_t) A.column_index[(std::size_t) e]]++;
+            c[k] = r;
+            v[k] = A.value[(std::size_t) e];
+        }
+    return csr_matrix::Matrix(A.columns, A.rows, (csr_matrix::size_type) nnz, 1, std::move(p), std::move(c), std::move(v));
+}
+
+// (transposed: the kernel multiplies by A' -- x has `rows` entries and y has `columns`)
 std::ostream & print_common(std::ostream & o, std::string const & name, std::string const & path,
                             char const * format, long long rows, long long columns, long long nonzeros,
-                            std::size_t matrix_size)
+                            std::size_t matrix_size, bool transposed = false)
 {
     // (additive, only for a path with a reordering suffix: which order the rows got -- "__GP<n>" without METIS changes nothing,
     // "__GPX<n>" names this build's own partitioner, so that neither is taken for a METIS ordering)
@@ -77,8 +100,8 @@ std::ostream & print_common(std::ostream & o, std::string const & name, std::str
              << "\"columns\": " << columns << ",\n"
              << "\"nonzeros\": " << nonzeros << ",\n"
              << "\"matrix_size\": " << matrix_size << ",\n"
-             << "\"x_size\": " << sizeof(double) * (std::size_t) columns << ",\n"
-             << "\"y_size\": " << sizeof(double) * (std::size_t) rows;
+             << "\"x_size\": " << sizeof(double) * (std::size_t) (transposed ? rows : columns) << ",\n"
+             << "\"y_size\": " << sizeof(double) * (std::size_t) (transposed ? columns : rows);
 }
 
 bool is_master()
@@ -108,6 +131,8 @@ public:
     {
         guarded_init(matrix_path, [&] {
             A = load_csr(matrix_path, options, o, verbose);
+            if (options.transpose_on_host)
+                A = transposed_on_host(A);
             x = csr_matrix::value_array_type((std::size_t) A.columns, 1.0);
             y = csr_matrix::value_array_type((std::size_t) A.rows, 0.0);
         });
@@ -513,6 +538,42 @@ private:
     long long diagonal = 0;
 };
 
+// --transpose: A stays on the device as it is stored and every run adds A' x to y (x has rows entries, y has columns): no
+// transposed copy of the matrix is made, on the host or on the device
+class hip_csr_transposed_spmv_kernel : public hip_kernel_base
+{
+public:
+    using hip_kernel_base::hip_kernel_base;
+    void init(TraceConfig const &, std::ostream & o, bool verbose) override
+    {
+        auto const t0 = std::chrono::steady_clock::now();
+        guarded_init(matrix_path, [&] {
+            A = load_csr(matrix_path, options, o, verbose);
+            x.assign((std::size_t) A.rows, 1.0);
+            y.assign((std::size_t) A.columns, 0.0);
+        });
+        auto const t1 = std::chrono::steady_clock::now();
+        create_context();
+        check(spmv_hip_upload_csr_transposed(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(),
+                                             A.column_index.data(), A.value.data()), "upload_csr_transposed");
+        init_load_seconds = std::chrono::duration<double>(t1 - t0).count();
+        init_upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    }
+    std::string name() const override { return "hip-csr-spmv-transposed"; }
+    std::ostream & print(std::ostream & o) const override
+    {
+        print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size(), true);
+        o << ",\n\"transposed\": true";
+        return print_device(o) << "\n}";
+    }
+
+    double flops_per_run() const override { return 2.0 * A.num_entries; }
+    double bytes_per_run() const override { return 12.0 * A.row_ptr[(std::size_t) A.rows] + 4.0 * (A.rows + 1.0) + 8.0 * A.rows + 16.0 * A.columns; }
+
+private:
+    csr_matrix::Matrix A;
+};
+
 // --vectors K: Y += A X for K vectors in one multiply (spmv_hip_run_block).  Column c of X is x * (c + 1), x being what the
 // single-vector kernel multiplies (ones, or --x uniform); result() is Y row-major, rows x K.
 class hip_csr_multivec_spmv_kernel : public hip_kernel_base
@@ -691,6 +752,7 @@ std::unique_ptr<Kernel> make_spmv_kernel(SpmvFormat format, bool hip, std::strin
     case SpmvFormat::csr:
         if (hip && opt.symmetric) return std::make_unique<hip_csr_symmetric_spmv_kernel>(path, opt);
         if (hip && opt.vectors > 0) return std::make_unique<hip_csr_multivec_spmv_kernel>(path, opt);
+        if (hip && opt.transpose) return std::make_unique<hip_csr_transposed_spmv_kernel>(path, opt);
         if (hip) return std::make_unique<hip_csr_spmv_kernel>(path, opt);
         return std::make_unique<csr_spmv_kernel>(path, opt);
     case SpmvFormat::coo:

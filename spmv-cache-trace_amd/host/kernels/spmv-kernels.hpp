@@ -8,6 +8,8 @@
 //       No fallback: if the device library cannot run, init() throws kernel_error.
 //   hip_csr_symmetric_spmv_kernel (--symmetric)
 //       the stored triangle of a symmetric / skew-symmetric file multiplied as the whole matrix, each stored value read once.
+//   hip_csr_transposed_spmv_kernel (--transpose)
+//       y += A' x from the CSR arrays of A as they are (x has rows entries, y has columns); no transposed copy is made.
 //
 // All of them load the matrix in init() exactly as the reference does (Matrix Market file ->
 // format conversion, x = 1.0, y = 0.0, errors rewrapped as "<path>: <what>") and print the same
@@ -38,6 +40,10 @@ struct SpmvOptions
     unsigned hip_flags = 0;        // SPMV_HIP_FLAG_*
     bool symmetric = false;        // EXTENSION: multiply the stored triangle of a (skew-)symmetric file as the whole matrix
                                    // (hip-csr only: spmv_hip_upload_csr_symmetric, include/spmv_hip_symmetric.h)
+    bool transpose = false;        // EXTENSION: y += A' x from the arrays of A as stored (hip-csr, one device:
+                                   // spmv_hip_upload_csr_transposed, include/spmv_hip_transpose.h)
+    bool transpose_on_host = false; // the CPU CSR kernel multiplies the matrix transposed on the host: what --check compares
+                                   // --transpose with (set by the program, not by an option)
     int vectors = 0;               // EXTENSION: > 0: Y += A X for that many vectors (hip-csr, one device: include/spmv_hip_multivec.h)
 };
 

@@ -95,6 +95,7 @@ enum Key
     key_gpus,
     key_symmetric,
     key_vectors,
+    key_transpose,
 };
 
 bool parse_count(char const * arg, long long & out)
@@ -205,9 +206,25 @@ error_t parse_option(int key, char * arg, argp_state * state)
             argp_error(state, "vectors: expected an integer from 1 to 16");
         a.spmv.vectors = (int) n;
         break;
+    case key_transpose: a.spmv.transpose = true; break;
     case ARGP_KEY_END:
         if (a.list_perf_events)
             break;
+        if (a.spmv.transpose) {
+            // what --transpose runs on: hip-csr on one device (include/spmv_hip_transpose.h); anything else is refused here
+            // rather than multiplied some other way
+            if (a.spmv.symmetric)
+                argp_error(state, "--transpose cannot be combined with --symmetric: the matrix a stored triangle stands for is its own transpose");
+            if (a.spmv.vectors > 0)
+                argp_error(state, "--transpose cannot be combined with --vectors: there is no multi-vector transposed kernel");
+            if (a.kernel_type != KernelType::spmv || a.format != SpmvFormat::csr)
+                argp_error(state, "--transpose needs the CSR kernel on the GPU (--spmv-format hip-csr or --csr PATH): "
+                                  "there is no transposed COO, ELLPACK or hybrid kernel");
+            if (!a.hip && (!a.shortcut || a.device_given))
+                argp_error(state, "--transpose runs on the GPU only (--spmv-format hip-csr or --device hip): there is no CPU transposed kernel");
+            if (a.spmv.num_gpus > 1)
+                argp_error(state, "--transpose runs on one device: a row partition would need a reduction of y across devices (--gpus must be 1)");
+        }
         if (a.spmv.vectors > 0) {
             // what --vectors runs on: hip-csr on one device (include/spmv_hip_multivec.h); anything else is refused here
             if (a.spmv.symmetric)
@@ -328,6 +345,9 @@ int main(int argc, char ** argv)
          "EXTENSION (hip-csr, one device): multiply the stored triangle of a symmetric or skew-symmetric file (or a synthetic:...:tril "
          "spec) as the whole matrix -- y += (T + T' - diag T) x, or (T - T') x -- reading every stored value once; --check then "
          "compares with the CPU CSR kernel on the expanded matrix.  Partial sums meet in atomics: not bit-reproducible", 2},
+        {"transpose", key_transpose, nullptr, 0,
+         "EXTENSION (hip-csr, one device): y += A' x from the arrays of A as they are stored (x has rows entries, y has columns); "
+         "no transposed copy is made.  --check compares with the CPU CSR kernel on the matrix transposed on the host", 2},
         {"vectors", key_vectors, "K", 0,
          "EXTENSION (hip-csr, one device): Y += A X for K = 1 ... 16 vectors in one multiply, every stored entry read once; column c "
          "of X is x scaled by c + 1.  Flops count 2 nnz K; --check compares every column with the CPU CSR kernel", 2},
@@ -420,13 +440,19 @@ int main(int argc, char ** argv)
         int count = 0;
         if (spmv_hip_device_count(&count) == 0 && count > 0)
             args.hip = true;
-        else if (!args.spmv.symmetric && args.spmv.vectors == 0) // (--symmetric / --vectors fail below: nothing runs in its place)
+        else if (!args.spmv.symmetric && args.spmv.vectors == 0 && !args.spmv.transpose) // (those fail below: nothing runs in their place)
             std::cerr << "note: no usable HIP device: the CPU (OpenMP) kernel runs (--device hip makes this an error, --device cpu silences the note)\n";
     }
 
     if (args.spmv.symmetric && !args.hip) {
         std::cerr << "--symmetric: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU symmetric kernel "
                      "(nothing runs in its place)\n";
+        return EXIT_FAILURE;
+    }
+
+    if (args.spmv.transpose && !args.hip) {
+        std::cerr << "--transpose: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU transposed "
+                     "kernel (nothing runs in its place)\n";
         return EXIT_FAILURE;
     }
 
@@ -480,6 +506,11 @@ int main(int argc, char ** argv)
                 ref_options.symmetric = false;
                 ref_options.expand_symmetric = true;
             }
+            // (--transpose: the matrix transposed on the host by a stable counting sort -- again an independent path)
+            if (args.spmv.transpose) {
+                ref_options.transpose = false;
+                ref_options.transpose_on_host = true;
+            }
             ref_options.vectors = 0;
             double err = 0.0;
             int const k = std::max(1, args.spmv.vectors);
@@ -508,6 +539,7 @@ int main(int argc, char ** argv)
             }
             parity = ",\n\"parity\": {\"against\": \"csr-spmv (CPU, 1 thread)" +
                 std::string(args.spmv.symmetric ? " on the expanded matrix (expand_symmetry)" : "") +
+                std::string(args.spmv.transpose ? " on the matrix transposed on the host" : "") +
                 (args.spmv.vectors > 0 ? ", every one of the " + std::to_string(k) + " columns" : std::string()) + ", " +
                 std::to_string(args.profile + 1) + " accumulating runs\", \"max_relative_error\": ";
             char buf[64];

@@ -1,5 +1,5 @@
-"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h and spmv_hip_multivec.h (the C ABI
-of libspmv_hip.so).
+"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h and
+spmv_hip_transpose.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -19,10 +19,11 @@ if os.environ.get("SPMV_HIP_EXPERIMENTS") == "1":
 elif os.environ.get("SPMV_HIP_EXPERIMENTS", "").endswith(".so"):  # an ablation build of tools/ablate.sh
     LIB_PATH = os.path.abspath(os.environ["SPMV_HIP_EXPERIMENTS"])
 # the drop-in boundary (what an adapter of the reference binds) and the headers that include it (tuning switches; Level 2;
-# the symmetric multiply of a stored triangle; Y += A X for several vectors)
+# the symmetric multiply of a stored triangle; Y += A X for several vectors; y += A' x)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
-                                for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h")]
+                                for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
+                                          "spmv_hip_transpose.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -53,6 +54,8 @@ TRIANGLE_MIXED, TRIANGLE_LOWER, TRIANGLE_UPPER, TRIANGLE_DIAGONAL = 0, 1, 2, 3
 TRIANGLE_NAMES = {0: "mixed", 1: "lower", 2: "upper", 3: "diagonal"}
 # spmv_hip_multivec.h
 MV_MAX_VECTORS = 16
+# spmv_hip_transpose.h
+TR_MAX_WINDOWS = 8
 
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -120,6 +123,12 @@ SIGNATURES = {
     "spmv_hip_set_block_y": (C.c_int, [_vp, C.c_int, _vp]),
     "spmv_hip_get_block_y": (C.c_int, [_vp, C.c_int, _vp]),
     "spmv_hip_run_block": (C.c_int, [_vp]),
+    "spmv_hip_upload_csr_transposed": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "spmv_hip_tr_plan_preview": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int64]),
+    "spmv_hip_tr_plan_csr": (C.c_int, [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "spmv_hip_csr_spmv_t": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_tr_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
+    "spmv_hip_tr_plan_destroy": (None, [_vp]),
 }
 
 
@@ -285,6 +294,16 @@ class Context:
             col, val = _EMPTY_I32, _EMPTY_F64
         check(self.lib.spmv_hip_upload_csr_symmetric(self.h, rows, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, kind))
         self.rows, self.cols = rows, rows
+
+    def upload_csr_transposed(self, rows, cols, row_ptr, col, val):
+        """A (rows x cols) as it is: runs then add A' x to y; set_x takes rows entries, set_y / get_y take cols
+        (include/spmv_hip_transpose.h)."""
+        row_ptr, col, val = _i32(row_ptr), _i32(col), _f64(val)
+        nnz = int(row_ptr[rows]) if len(row_ptr) > rows >= 0 else -1
+        if len(col) == 0:
+            col, val = _EMPTY_I32, _EMPTY_F64
+        check(self.lib.spmv_hip_upload_csr_transposed(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data))
+        self.rows, self.cols = cols, rows  # of the operator that runs, A'
 
     def set_x(self, x):
         x = _f64(x)
@@ -480,6 +499,75 @@ class SymPlan:
     def symv(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
         """y += (T + T' - diag(T)) x (or (T - T') x); raw device addresses, d_x != d_y."""
         check(self.lib.spmv_hip_csr_symv(self.h, d_row_ptr, d_col, d_val, d_x, d_y, stream))
+
+
+TR_INFO_KEYS = ["ranges", "rows_per_range", "max_windows", "windows", "lds_bytes", "spilled_entries", "atomic_bytes",
+                "stored_entries", "rows", "cols", "device_bytes", "streamed_bytes", "window_slots", "most_entries_in_a_range"]
+
+
+def tr_plan_preview(rows, cols, row_ptr, col, max_windows=0, window_doubles=0, table=True):
+    """What TrPlan would choose for these HOST arrays, without a device: (info dict, window table).  The table is an int32
+    array [ranges, max_windows, 2] of {first column, length} (length 0: unused), or None with table=False."""
+    lib = load()
+    row_ptr, col = _i32(row_ptr), _i32(col)
+    if len(row_ptr) < rows + 1:
+        raise ValueError("row_ptr needs rows + 1 entries")
+    if len(col) == 0:
+        col = _EMPTY_I32
+    out = np.zeros(len(TR_INFO_KEYS), dtype=np.int64)
+    check(lib.spmv_hip_tr_plan_preview(rows, cols, row_ptr.ctypes.data, col.ctypes.data, max_windows, window_doubles,
+                                       out.ctypes.data, len(out), None, 0))
+    info = dict(zip(TR_INFO_KEYS, out.tolist()))
+    if not table:
+        return info, None
+    win = np.zeros((info["ranges"], info["max_windows"], 2), dtype=np.int32)
+    check(lib.spmv_hip_tr_plan_preview(rows, cols, row_ptr.ctypes.data, col.ctypes.data, max_windows, window_doubles,
+                                       out.ctypes.data, len(out), win.ctypes.data if win.size else None, win.size))
+    return info, win
+
+
+class TrPlan:
+    """Level-2 plan of the transposed multiply y += A' x (spmv_hip_tr_plan_*): host row_ptr, device columns.
+    max_windows / window_doubles = 0: automatic (small values force spilled entries)."""
+
+    INFO_KEYS = TR_INFO_KEYS
+
+    def __init__(self, rows, cols, host_row_ptr, d_col, max_windows=0, window_doubles=0, stream=0):
+        self.lib = load()
+        self.h = None
+        rp = _i32(host_row_ptr)
+        if len(rp) < rows + 1:
+            raise ValueError("host_row_ptr needs rows + 1 entries")
+        h = _vp()
+        check(self.lib.spmv_hip_tr_plan_csr(C.byref(h), rows, cols, rp.ctypes.data, d_col, max_windows, window_doubles, stream))
+        self.h = h
+        self.rows, self.cols = rows, cols
+
+    def close(self):
+        if self.h:
+            self.lib.spmv_hip_tr_plan_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.int64)
+        check(self.lib.spmv_hip_tr_plan_info(self.h, out, len(out)))
+        return dict(zip(self.INFO_KEYS, out.tolist()))
+
+    def spmv_t(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
+        """y += A' x; raw device addresses, d_x (rows entries) != d_y (cols entries)."""
+        check(self.lib.spmv_hip_csr_spmv_t(self.h, d_row_ptr, d_col, d_val, d_x, d_y, stream))
 
 
 def _dev(a):
