@@ -25,6 +25,14 @@ void free_ctx_matrix(spmv_hip_ctx * c)
         spmv_hip_tr_plan_destroy(c->tr_plan);
         c->tr_plan = nullptr;
     }
+    if (c->f32_plan) {
+        spmv_hip_f32_plan_destroy(c->f32_plan);
+        c->f32_plan = nullptr;
+    }
+    if (c->d_val32) {
+        (void) hipFree(c->d_val32);
+        c->d_val32 = nullptr;
+    }
     if (c->mv_plan) {
         spmv_hip_mv_plan_destroy(c->mv_plan);
         c->mv_plan = nullptr;
@@ -746,6 +754,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
     case 1: rc = csr_run(); break;
     case 5: rc = spmv_hip_csr_symv(c->sym_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
     case 6: rc = spmv_hip_csr_spmv_t(c->tr_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
+    case 7: rc = spmv_hip_csr_spmv_f32(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
     case 2:
         rc = c->as_csr ? csr_run() : ctx_coo_run(c, c->nnz, c->d_idx, c->d_col, c->d_val);
         break;
@@ -888,6 +897,12 @@ int spmv_hip_ctx_info(spmv_hip_ctx * c, int64_t * out, int n)
         spmv_hip_tr_plan_info(c->tr_plan, ti, SPMV_HIP_TR_INFO);
         v[6] = ti[0];
         v[15] = ti[11];
+    }
+    if (c->f32_plan) { // format 7: workgroups and streamed bytes of the fp32-value plan
+        int64_t fi[SPMV_HIP_F32_INFO] = {0};
+        spmv_hip_f32_plan_info(c->f32_plan, fi, SPMV_HIP_F32_INFO);
+        v[6] = fi[11];
+        v[15] = fi[8];
     }
     if (c->d_prow)
         v[14] += c->coo_panel_blocks; // COO (part) in column panels: workgroups per panel

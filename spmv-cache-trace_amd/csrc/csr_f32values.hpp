@@ -1,0 +1,244 @@
+// csr_f32values.hpp -- y += fl32(A) x (include/spmv_hip_f32values.h): the plain path of csr_wavetile_kernel with the value
+// stream at 4 bytes per entry.  A wave per tile of up to 512 entries counted from a 4-aligned entry, four waves per workgroup,
+// each with an LDS slice of its own; per lane and quad ONE 16-byte load of four columns and ONE 16-byte load of four floats,
+// both quads of a lane issued before anything waits; then the four x gathers, four widenings (v_cvt_f64_f32: exact, denormals
+// included) and four fp64 multiplies, the rounded products parked in the slice and added up row by row by L lanes exactly as
+// the plain tile does (tile_common.hpp: tile_row_sum, group_sum).  No atomics anywhere: a row is written by one lane.
+// A row longer than a tile is a tile of its own: the whole wave in registers, 512 entries per step, one butterfly at the end.
+#pragma once
+
+#include "tile_common.hpp"
+
+namespace spmv {
+
+// descriptor {first row, first entry, meta, 0}; tile w ends where tile w + 1 starts (the table has tiles + 1 records)
+// meta = longest row (stream tiles: <= 512) | log2(lanes per row) << 16 | fast << 25 | uniform << 26
+constexpr int kF32Tile = 512;
+constexpr int kF32TileRows = 64;
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// tile_products_wide's rules: lanes past the tile's end re-read its last quad; entries in front of the tile that share its
+// first quad are multiplied and never read back
+template <int QUADS, bool X32>
+__device__ __forceinline__ void tile_products_f32(double * prod, const int32_t * __restrict__ jt, const float * __restrict__ at,
+                                                  const double * __restrict__ x, int last, int lane)
+{
+    v4i c[QUADS];
+    v4f v[QUADS];
+#pragma unroll
+    for (int q = 0; q < QUADS; ++q) {
+        int o = 256 * q + 4 * lane;
+        o = o < last ? o : last;
+        c[q] = *reinterpret_cast<const v4i *>(jt + o);
+        v[q] = *reinterpret_cast<const v4f *>(at + o);
+    }
+#pragma unroll
+    for (int q = 0; q < QUADS; ++q) {
+        const int o = 256 * q + 4 * lane;
+        if (o <= last) {
+            const double q0 = (double) v[q].x * gather_x<X32>(x, c[q].x);
+            const double q1 = (double) v[q].y * gather_x<X32>(x, c[q].y);
+            const double q2 = (double) v[q].z * gather_x<X32>(x, c[q].z);
+            const double q3 = (double) v[q].w * gather_x<X32>(x, c[q].w);
+            v2d * dst = reinterpret_cast<v2d *>(prod + o);
+            dst[0] = v2d{q0, q1};
+            dst[1] = v2d{q2, q3};
+        }
+    }
+}
+
+// long_row_sum (tile_common.hpp) over float values: the 4-aligned interior [ka, kz) in quads, two per lane and step in
+// flight, four accumulators per lane; the up to three entries in front of ka and behind kz by single lanes.  Nothing is read
+// outside [k0, k1).
+template <bool X32>
+__device__ __forceinline__ double long_row_sum_f32(const int32_t * __restrict__ j, const float * __restrict__ a,
+                                                   const double * __restrict__ x, int k0, int k1, int lane)
+{
+    double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
+    const int ka = (k0 + 3) & ~3, kz = k1 & ~3;
+    if (ka >= kz) {
+        for (int k = k0 + lane; k < k1; k += kWave)
+            z0 += (double) a[k] * x[j[k]];
+        return group_sum<kWave>(z0);
+    }
+    if (lane < ka - k0)
+        z0 += (double) a[k0 + lane] * x[j[k0 + lane]];
+    if (lane >= 4 && lane - 4 < k1 - kz)
+        z1 += (double) a[kz + lane - 4] * x[j[kz + lane - 4]];
+    for (int o = ka + 4 * lane; o < kz; o += 2 * 4 * kWave) {
+        const bool two = o + 4 * kWave < kz;
+        const int o2 = two ? o + 4 * kWave : o;
+        const v4i ca = *reinterpret_cast<const v4i *>(j + o), cb = *reinterpret_cast<const v4i *>(j + o2);
+        const v4f va = *reinterpret_cast<const v4f *>(a + o), vb = *reinterpret_cast<const v4f *>(a + o2);
+        const double xa0 = gather_x<X32>(x, ca.x), xa1 = gather_x<X32>(x, ca.y), xa2 = gather_x<X32>(x, ca.z), xa3 = gather_x<X32>(x, ca.w);
+        const double xb0 = gather_x<X32>(x, cb.x), xb1 = gather_x<X32>(x, cb.y), xb2 = gather_x<X32>(x, cb.z), xb3 = gather_x<X32>(x, cb.w);
+        z0 += (double) va.x * xa0;
+        z1 += (double) va.y * xa1;
+        z2 += (double) va.z * xa2;
+        z3 += (double) va.w * xa3;
+        if (two) {
+            z0 += (double) vb.x * xb0;
+            z1 += (double) vb.y * xb1;
+            z2 += (double) vb.z * xb2;
+            z3 += (double) vb.w * xb3;
+        }
+    }
+    return group_sum<kWave>((z0 + z1) + (z2 + z3));
+}
+
+template <bool X32>
+__global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const int4 * __restrict__ desc, const int32_t * __restrict__ p,
+                                                               const int32_t * __restrict__ j, const float * __restrict__ a,
+                                                               const double * __restrict__ x, double * y, int exact_order)
+{
+    constexpr int TILE = kF32Tile, QUADS = TILE / 256;
+    __shared__ __attribute__((aligned(16))) double prod_all[4][TILE + 4];
+    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
+    const int lane = (int) __lane_id();
+    const int w = (int) blockIdx.x * 4 + wave;
+    if (w >= ntiles)
+        return; // whole wave leaves; no workgroup barrier in this kernel
+    double * prod = prod_all[wave];
+    const TilePair dp = load_tile_pair(desc, w);
+    const int r0 = __builtin_amdgcn_readfirstlane(dp.d0.x);
+    const int k0 = __builtin_amdgcn_readfirstlane(dp.d0.y);
+    const int meta = __builtin_amdgcn_readfirstlane(dp.d0.z);
+    const int r1 = __builtin_amdgcn_readfirstlane(dp.d1.x);
+    const int k1 = __builtin_amdgcn_readfirstlane(dp.d1.y);
+    const int nrows = r1 - r0;
+    const int kb = k0 & ~3;
+    const int maxlen = meta & 0xFFFF;
+    const int lanes_log2 = (meta >> kTileMetaLanesShift) & 0x7;
+
+    if (meta & kTileMetaFast) {
+        // ---- stream tile: rows << lanes_log2 <= 64, not empty, its last quad inside the arrays ----
+        const int sub = lane >> lanes_log2;
+        const int part = lane & ((1 << lanes_log2) - 1);
+        const int rowi = sub < nrows ? sub : nrows - 1;
+        int ps, pe;
+        if (meta & kTileMetaUniform) { // all rows equally long: row_ptr is not read
+            ps = k0 + rowi * maxlen;
+            pe = ps + maxlen;
+        } else {
+            const int32_t * pt = p + r0;
+            ps = pt[rowi];
+            pe = pt[rowi + 1];
+        }
+        const double yv = y[r0 + rowi];
+        const int last = (k1 - 1 - kb) & ~3;
+        tile_products_f32<QUADS, X32>(prod, j + kb, a + kb, x, last, lane);
+        // same-wave LDS operations execute in order; the fences only pin the compiler
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int s = ps - kb, e_row = pe - kb;
+        double z;
+        if (lanes_log2 == 0) { // one lane per row, left to right: the reference's order
+            z = tile_row_sum<1>(prod, s, e_row, 0, maxlen);
+        } else {
+            const int trips = (maxlen + (1 << lanes_log2) - 1) >> lanes_log2;
+            switch (lanes_log2) {
+            case 1: z = tile_row_sum<2>(prod, s, e_row, part, trips); break;
+            case 2: z = tile_row_sum<4>(prod, s, e_row, part, trips); break;
+            case 3: z = tile_row_sum<8>(prod, s, e_row, part, trips); break;
+            case 4: z = tile_row_sum<16>(prod, s, e_row, part, trips); break;
+            case 5: z = tile_row_sum<32>(prod, s, e_row, part, trips); break;
+            default: z = tile_row_sum<64>(prod, s, e_row, part, trips); break;
+            }
+        }
+        if (sub < nrows && part == 0)
+            y[r0 + sub] = yv + z;
+    } else if (k1 - kb <= TILE) {
+        // ---- a tile of empty rows, or the tile whose last quad is not whole (the ragged end of the arrays): entry by entry,
+        // one lane per row, left to right
+        for (int k = k0 + lane; k < k1; k += kWave)
+            prod[k - kb] = (double) a[k] * x[j[k]];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int r = lane; r < nrows; r += kWave) {
+            const int s = p[r0 + r] - kb, e_row = p[r0 + r + 1] - kb;
+            double z = 0.0;
+            for (int k = s; k < e_row; ++k)
+                z += prod[k];
+            y[r0 + r] = y[r0 + r] + z;
+        }
+    } else if (!exact_order) {
+        // ---- one row longer than a tile: the whole wave, in registers ----
+        const double z = long_row_sum_f32<X32>(j, a, x, k0, k1, lane);
+        if (lane == 0)
+            y[r0] = y[r0] + z;
+    } else {
+        // ---- ... in the reference's order: lane 0 adds tiles of products left to right ----
+        double z = 0.0;
+        for (int t0 = k0; t0 < k1; t0 += TILE) {
+            const int t1 = (t0 + TILE < k1) ? t0 + TILE : k1;
+            for (int k = t0 + lane; k < t1; k += kWave)
+                prod[k - t0] = (double) a[k] * x[j[k]];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (lane == 0)
+                for (int k = 0; k < t1 - t0; ++k)
+                    z += prod[k];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        if (lane == 0)
+            y[r0] = y[r0] + z;
+    }
+}
+
+// spmv_hip_narrow_values: out[k] = (float) value[k]; per workgroup {values that changed, finite values that became infinite,
+// index of the first of either kind} and the largest relative change, reduced by the host (no atomics: the same numbers on
+// every run)
+struct NarrowCounts {
+    long long inexact, overflow, first_inexact, first_overflow;
+    double max_rel;
+};
+
+static __global__ __launch_bounds__(256) void narrow_values_kernel(long long n, const double * __restrict__ value, float * __restrict__ out,
+                                                                   NarrowCounts * __restrict__ counts)
+{
+    __shared__ NarrowCounts part[256];
+    NarrowCounts c{0, 0, -1, -1, 0.0};
+    for (long long k = (long long) blockIdx.x * 256 + threadIdx.x; k < n; k += (long long) gridDim.x * 256) {
+        const double v = value[k];
+        const float f = (float) v;
+        out[k] = f;
+        const double back = (double) f;
+        if (back != v && v == v) {
+            if (__builtin_isinf(back)) {
+                ++c.overflow;
+                if (c.first_overflow < 0)
+                    c.first_overflow = k;
+            } else {
+                ++c.inexact;
+                if (c.first_inexact < 0)
+                    c.first_inexact = k;
+                const double rel = __builtin_fabs(back - v) / __builtin_fabs(v);
+                c.max_rel = rel > c.max_rel ? rel : c.max_rel;
+            }
+        }
+    }
+    part[threadIdx.x] = c;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int) threadIdx.x < s) {
+            NarrowCounts & m = part[threadIdx.x];
+            const NarrowCounts o = part[threadIdx.x + s];
+            m.inexact += o.inexact;
+            m.overflow += o.overflow;
+            m.first_inexact = m.first_inexact < 0 ? o.first_inexact : (o.first_inexact < 0 ? m.first_inexact : (m.first_inexact < o.first_inexact ? m.first_inexact : o.first_inexact));
+            m.first_overflow = m.first_overflow < 0 ? o.first_overflow : (o.first_overflow < 0 ? m.first_overflow : (m.first_overflow < o.first_overflow ? m.first_overflow : o.first_overflow));
+            m.max_rel = o.max_rel > m.max_rel ? o.max_rel : m.max_rel;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        counts[blockIdx.x] = part[0];
+}
+
+} // namespace spmv

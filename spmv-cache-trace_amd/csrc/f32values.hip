@@ -1,0 +1,402 @@
+// f32values.hip -- include/spmv_hip_f32values.h: y += fl32(A) x with the values stored and streamed as 4-byte floats.  The plan
+// cuts the rows into wave tiles on the host from row_ptr alone (the plain tiles of plan_csr.hip: lanes per row from the tile's
+// longest row, at most 16 entries per lane); the kernel is csr_f32values.hpp.
+#include "internal.hpp"
+#include "csr_f32values.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <new>
+
+using namespace spmvi;
+
+struct spmv_hip_f32_plan {
+    int32_t rows = 0, cols = 0, nnz = 0;
+    unsigned flags = 0;
+    int ntiles = 0, long_tiles = 0, uniform_tiles = 0, scalar_tiles = 0, longest = 0;
+    long long streamed_bytes = 0;
+    size_t device_bytes = 0;
+    int4 * d_desc = nullptr; // ntiles + 1 records
+};
+
+namespace {
+
+int check_host(int32_t rows, int32_t cols, const int32_t * rp, unsigned flags)
+{
+    if (rows < 0 || cols < 0 || !rp)
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
+    if (flags & ~SPMV_HIP_FLAG_EXACT_ORDER)
+        return fail(SPMV_HIP_ERR_INVALID, "unknown flag bits (0 or SPMV_HIP_FLAG_EXACT_ORDER)");
+    if (rp[0] != 0)
+        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[0] must be 0");
+    for (int32_t r = 0; r < rows; ++r)
+        if (rp[r + 1] < rp[r])
+            return fail(SPMV_HIP_ERR_INVALID, "row_ptr must be non-decreasing");
+    return SPMV_HIP_OK;
+}
+
+// what the preview and the plan share: every number of plan_info and the descriptors
+struct HostPlan {
+    spmv_hip_f32_plan numbers;
+    std::vector<int4> desc;
+};
+
+int lanes_for(int len)
+{
+    int l = 0;
+    while (l < 6 && (16 << l) < len)
+        ++l;
+    return l;
+}
+
+void plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, unsigned flags)
+{
+    spmv_hip_f32_plan & pl = hp.numbers;
+    const int32_t nnz = p[rows];
+    const bool exact = (flags & SPMV_HIP_FLAG_EXACT_ORDER) != 0;
+    pl.rows = rows;
+    pl.cols = cols;
+    pl.nnz = nnz;
+    pl.flags = flags;
+    for (int32_t r = 0; r < rows; ++r)
+        pl.longest = std::max(pl.longest, p[r + 1] - p[r]);
+    if (rows == 0 || cols == 0 || nnz == 0)
+        return; // the multiply does nothing
+    long long row_ptr_bytes = 0;
+    for (int32_t r = 0; r < rows;) {
+        const int32_t k0 = p[r], kb = k0 & ~3;
+        if ((long long) p[r + 1] - kb > spmv::kF32Tile) {
+            // a row longer than a tile: a tile of its own, the whole wave (one lane in exact order)
+            const int len = p[r + 1] - k0;
+            hp.desc.push_back(make_int4(r, k0, std::min(len, 0xFFFF) | ((exact ? 0 : 6) << spmv::kTileMetaLanesShift), 0));
+            ++pl.long_tiles;
+            ++r;
+            continue;
+        }
+        int32_t r1 = r;
+        int maxlen = 0, minlen = INT32_MAX;
+        while (r1 < rows && r1 - r < spmv::kF32TileRows && (long long) p[r1 + 1] - kb <= spmv::kF32Tile) {
+            const int len = p[r1 + 1] - p[r1];
+            if (!exact && r1 > r) { // only as many rows as the wave has lanes for at <= 16 entries per lane
+                const int l = lanes_for(std::max(maxlen, len));
+                if (l > 0 && ((r1 - r + 1) << l) > 64)
+                    break;
+            }
+            maxlen = std::max(maxlen, len);
+            minlen = std::min(minlen, len);
+            ++r1;
+        }
+        const int lanes_log2 = exact ? 0 : lanes_for(maxlen);
+        const int32_t k1 = p[r1];
+        const bool fast = k1 > k0 && (long long) ((k1 - 1) & ~3) + 4 <= nnz;
+        const bool uniform = fast && minlen == maxlen;
+        hp.desc.push_back(make_int4(r, k0, maxlen | (lanes_log2 << spmv::kTileMetaLanesShift) | (fast ? spmv::kTileMetaFast : 0) |
+                                               (uniform ? spmv::kTileMetaUniform : 0), 0));
+        if (uniform)
+            ++pl.uniform_tiles;
+        else
+            row_ptr_bytes += 4LL * (r1 - r + 1);
+        if (!fast)
+            ++pl.scalar_tiles;
+        r = r1;
+    }
+    pl.ntiles = (int) hp.desc.size();
+    hp.desc.push_back(make_int4(rows, nnz, 0, 0));
+    pl.device_bytes = hp.desc.size() * sizeof(int4);
+    pl.streamed_bytes = 8LL * nnz + row_ptr_bytes + 16LL * rows + 8LL * cols + 16LL * (pl.ntiles + 1);
+}
+
+void plan_numbers(const spmv_hip_f32_plan & pl, int64_t * out, int n)
+{
+    const int64_t v[SPMV_HIP_F32_INFO] = {pl.rows, pl.cols, pl.nnz, pl.ntiles, pl.long_tiles, pl.longest, pl.flags,
+                                          (int64_t) pl.device_bytes, pl.streamed_bytes, pl.uniform_tiles, pl.scalar_tiles,
+                                          (pl.ntiles + 3) / 4};
+    for (int i = 0; i < n && i < SPMV_HIP_F32_INFO; ++i)
+        out[i] = v[i];
+}
+
+// the host plan onto the current device
+int build_plan(spmv_hip_f32_plan ** out, HostPlan const & hp, hipStream_t s)
+{
+    spmv_hip_f32_plan * pl = new (std::nothrow) spmv_hip_f32_plan(hp.numbers);
+    if (!pl)
+        return fail(SPMV_HIP_ERR_ALLOC, "plan allocation failed");
+    if (!hp.desc.empty()) {
+        hipError_t e = hipMalloc((void **) &pl->d_desc, hp.desc.size() * sizeof(int4));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(pl->d_desc, hp.desc.data(), hp.desc.size() * sizeof(int4), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            spmv_hip_f32_plan_destroy(pl);
+            return fail_hip(e, "fp32-value plan: tile descriptors");
+        }
+    }
+    *out = pl;
+    return SPMV_HIP_OK;
+}
+
+struct NarrowResult {
+    long long inexact = 0, overflow = 0, first_inexact = -1, first_overflow = -1;
+    double max_rel = 0.0;
+};
+
+NarrowResult narrow_host(int64_t n, const double * value, float * out)
+{
+    NarrowResult c;
+    for (int64_t k = 0; k < n; ++k) {
+        const double v = value[k];
+        const float f = static_cast<float>(v);
+        out[k] = f;
+        const double back = static_cast<double>(f);
+        if (back != v && v == v) {
+            if (std::isinf(back)) {
+                ++c.overflow;
+                if (c.first_overflow < 0)
+                    c.first_overflow = k;
+            } else {
+                ++c.inexact;
+                if (c.first_inexact < 0)
+                    c.first_inexact = k;
+                c.max_rel = std::max(c.max_rel, std::fabs(back - v) / std::fabs(v));
+            }
+        }
+    }
+    return c;
+}
+
+int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_err)
+{
+    if (c.overflow > 0) {
+        char text[160];
+        std::snprintf(text, sizeof text, "%lld finite value(s) are infinite as floats (the first is entry %lld)", c.overflow, c.first_overflow);
+        return fail(SPMV_HIP_ERR_OVERFLOW, text);
+    }
+    if (inexact)
+        *inexact = c.inexact;
+    if (max_rel_err)
+        *max_rel_err = c.max_rel;
+    return SPMV_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int spmv_hip_narrow_values_host(int64_t n, const double * value, float * out, int64_t * inexact, double * max_rel_err)
+{
+    if (n < 0 || (n > 0 && (!value || !out)))
+        return fail(SPMV_HIP_ERR_INVALID, "n < 0, or value / out null");
+    return narrow_report(narrow_host(n, value, out), inexact, max_rel_err);
+}
+
+int spmv_hip_narrow_values(int64_t n, const double * d_value, float * d_out, int64_t * inexact, double * max_rel_err, void * stream)
+{
+    if (n < 0 || (n > 0 && (!d_value || !d_out)))
+        return fail(SPMV_HIP_ERR_INVALID, "n < 0, or d_value / d_out null");
+    NarrowResult c;
+    if (n > 0) {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const int blocks = (int) std::min<int64_t>(1024, (n + 255) / 256);
+        spmv::NarrowCounts * d_counts = nullptr;
+        HIP_TRY(hipMalloc((void **) &d_counts, (size_t) blocks * sizeof(spmv::NarrowCounts)));
+        std::vector<spmv::NarrowCounts> counts((size_t) blocks);
+        hipLaunchKernelGGL(spmv::narrow_values_kernel, dim3((unsigned) blocks), dim3(256), 0, s, (long long) n, d_value, d_out, d_counts);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(counts.data(), d_counts, counts.size() * sizeof(spmv::NarrowCounts), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        (void) hipFree(d_counts);
+        if (e != hipSuccess)
+            return fail_hip(e, "narrow_values");
+        auto first = [](long long a, long long b) { return a < 0 ? b : (b < 0 ? a : std::min(a, b)); };
+        for (auto const & b : counts) {
+            c.inexact += b.inexact;
+            c.overflow += b.overflow;
+            c.first_inexact = first(c.first_inexact, b.first_inexact);
+            c.first_overflow = first(c.first_overflow, b.first_overflow);
+            c.max_rel = std::max(c.max_rel, b.max_rel);
+        }
+    }
+    return narrow_report(c, inexact, max_rel_err);
+}
+
+int spmv_hip_f32_plan_preview(int32_t rows, int32_t cols, const int32_t * host_row_ptr, unsigned flags, int64_t * out, int n,
+                              int32_t * tile_table, int64_t tile_table_ints)
+{
+    if (!out || n < 0 || tile_table_ints < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "out is null, or a negative count");
+    int rc;
+    if ((rc = check_host(rows, cols, host_row_ptr, flags)) != 0)
+        return rc;
+    HostPlan hp;
+    try {
+        plan_host(hp, rows, cols, host_row_ptr, flags);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "fp32-value plan: host memory");
+    }
+    const int nt = hp.numbers.ntiles;
+    if (tile_table) {
+        if (4LL * nt > tile_table_ints)
+            return fail(SPMV_HIP_ERR_INVALID, "tile_table is too small: it takes 4 int32 values per tile");
+        for (int w = 0; w < nt; ++w) {
+            tile_table[4 * w] = hp.desc[(size_t) w].x;
+            tile_table[4 * w + 1] = hp.desc[(size_t) w].y;
+            tile_table[4 * w + 2] = hp.desc[(size_t) w + 1].x - hp.desc[(size_t) w].x;
+            tile_table[4 * w + 3] = (hp.desc[(size_t) w].z >> spmv::kTileMetaLanesShift) & 7;
+        }
+    }
+    plan_numbers(hp.numbers, out, n);
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_f32_plan_csr(spmv_hip_f32_plan ** plan, int32_t rows, int32_t cols, const int32_t * host_row_ptr, unsigned flags,
+                          void * stream)
+{
+    if (!plan)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    *plan = nullptr;
+    int rc;
+    if ((rc = check_host(rows, cols, host_row_ptr, flags)) != 0)
+        return rc;
+    HostPlan hp;
+    try {
+        plan_host(hp, rows, cols, host_row_ptr, flags);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "fp32-value plan: host memory");
+    }
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1)
+        return fail(SPMV_HIP_ERR_NO_DEVICE, "no HIP device visible");
+    return build_plan(plan, hp, static_cast<hipStream_t>(stream));
+}
+
+int spmv_hip_csr_spmv_f32(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
+                          const float * d_value, const double * d_x, double * d_y, void * stream)
+{
+    if (!pl)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    if (d_x && (const void *) d_x == (const void *) d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
+    if (pl->ntiles == 0) // rows, cols or nnz of zero
+        return SPMV_HIP_OK;
+    if (!d_row_ptr || !d_column_index || !d_value || !d_x || !d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
+    if (!aligned16(d_column_index) || !aligned16(d_value))
+        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
+    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
+    if ((long long) pl->cols * 8 < (1LL << 32))
+        hipLaunchKernelGGL(spmv::csr_f32values_kernel<true>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
+    else
+        hipLaunchKernelGGL(spmv::csr_f32values_kernel<false>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_f32_plan_info(const spmv_hip_f32_plan * pl, int64_t * out, int n)
+{
+    if (!pl || !out || n < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "plan/out null");
+    plan_numbers(*pl, out, n);
+    return SPMV_HIP_OK;
+}
+
+void spmv_hip_f32_plan_destroy(spmv_hip_f32_plan * pl)
+{
+    if (!pl)
+        return;
+    if (pl->d_desc)
+        (void) hipFree(pl->d_desc);
+    delete pl;
+}
+
+// ---- Level 1 --------------------------------------------------------------------------------------------------------------------
+
+int spmv_hip_upload_csr_f32values(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
+                                  const int32_t * column_index, const double * value, int allow_rounding)
+{
+    if (!c)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
+    if (c->multi)
+        return fail(SPMV_HIP_ERR_STATE, "the fp32-value multiply runs on one device (a context of spmv_hip_create)");
+    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
+    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
+    int rc = check_host(rows, cols, row_ptr, flags);
+    if (rc != 0)
+        return rc;
+    if (row_ptr[rows] != nnz)
+        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
+    bool bad = false;
+    for (int32_t e = 0; e < nnz; ++e)
+        bad |= column_index[e] < 0 || column_index[e] >= cols;
+    if (bad)
+        return fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)");
+    // everything that can refuse the matrix happens before anything is freed or copied
+    std::vector<float> narrow;
+    HostPlan hp;
+    try {
+        narrow.resize((size_t) nnz);
+        const NarrowResult nr = narrow_host(nnz, value, narrow.data());
+        if ((rc = narrow_report(nr, nullptr, nullptr)) != 0)
+            return rc;
+        if (nr.inexact > 0 && !allow_rounding) {
+            char text[200];
+            std::snprintf(text, sizeof text, "%lld value(s) are not floats (the first is entry %lld, relative change at most %.3g) and allow_rounding is 0",
+                          nr.inexact, nr.first_inexact, nr.max_rel);
+            return fail(SPMV_HIP_ERR_INVALID, text);
+        }
+        plan_host(hp, rows, cols, row_ptr, flags);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "fp32-value upload: host memory");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_ctx_matrix(c);
+    if ((rc = build_plan(&c->f32_plan, hp, c->stream)) != 0)
+        return rc;
+    c->rows = rows;
+    c->cols = cols;
+    c->nnz = nnz;
+    auto alloc = [&](void ** p, size_t bytes) -> int {
+        hipError_t e = hipMalloc(p, bytes + 64);
+        if (e != hipSuccess)
+            return fail_hip(e, "hipMalloc");
+        c->bytes += bytes + 64;
+        return SPMV_HIP_OK;
+    };
+    auto cleanup = [&](int code) {
+        std::string const why = last_error_text();
+        free_ctx_matrix(c);
+        set_last_error_text(why);
+        return code;
+    };
+    if ((rc = alloc((void **) &c->d_ptr, ((size_t) rows + 1) * sizeof(int32_t))) != 0 ||
+        (rc = alloc((void **) &c->d_col, (size_t) nnz * sizeof(int32_t))) != 0 ||
+        (rc = alloc((void **) &c->d_val32, (size_t) nnz * sizeof(float))) != 0 ||
+        (rc = alloc((void **) &c->d_x, (size_t) cols * sizeof(double))) != 0 ||
+        (rc = alloc((void **) &c->d_y, (size_t) rows * sizeof(double))) != 0)
+        return cleanup(rc);
+    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, ((size_t) rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz > 0)
+        e = hipMemcpyAsync(c->d_col, column_index, (size_t) nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz > 0)
+        e = hipMemcpyAsync(c->d_val32, narrow.data(), (size_t) nnz * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->d_x, 0, (size_t) cols * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->d_y, 0, (size_t) rows * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess)
+        return cleanup(fail_hip(e, "upload (host arrays -> device)"));
+    c->bytes += c->f32_plan->device_bytes;
+    c->format = 7;
+    return SPMV_HIP_OK;
+}
+
+} // extern "C"

@@ -10,12 +10,14 @@
 //   symmetric.hip    the multiply of a stored triangle as the (skew-)symmetric matrix it stands for (spmv_hip_symmetric.h)
 //   multivec.hip     Y += A X for up to 16 vectors in one pass over a CSR matrix (spmv_hip_multivec.h)
 //   transpose.hip    y += A' x from the CSR arrays of A as they are (spmv_hip_transpose.h)
+//   f32values.hip    y += fl32(A) x with the values stored as 4-byte floats (spmv_hip_f32values.h)
 #pragma once
 
 #include "spmv_hip_plan.h"
 #include "spmv_hip_symmetric.h"
 #include "spmv_hip_multivec.h"
 #include "spmv_hip_transpose.h"
+#include "spmv_hip_f32values.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -197,13 +199,16 @@ struct spmv_hip_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     int format = 0; // 0 none, 1 csr, 2 coo, 3 ell, 4 hybrid (ell + coo remainder), 5 stored triangle of a (skew-)symmetric matrix,
-                    // 6 csr multiplied transposed (rows / cols are those of the operator that runs, A')
+                    // 6 csr multiplied transposed (rows / cols are those of the operator that runs, A'),
+                    // 7 csr with the values as 4-byte floats (d_val32; no fp64 values are kept)
     int32_t rows = 0, cols = 0, nnz = 0, row_length = 0, nnz2 = 0;
     int csr_algorithm = SPMV_HIP_CSR_AUTO;
     int csr_lanes = 0;
     spmv_hip_plan * plan = nullptr;
     spmv_hip_sym_plan * sym_plan = nullptr; // format 5 (symmetric.hip)
     spmv_hip_tr_plan * tr_plan = nullptr;   // format 6 (transpose.hip)
+    spmv_hip_f32_plan * f32_plan = nullptr; // format 7 (f32values.hip)
+    float * d_val32 = nullptr;              // ... its values
     // block vectors of spmv_hip_run_block (multivec.hip; format 1 only): X (cols x block_k) and Y (rows x block_k), row-major,
     // apart from d_x / d_y; the plan is made on the first run_block after the matrix or k changed
     spmv_hip_mv_plan * mv_plan = nullptr;

@@ -8,6 +8,7 @@
 #include "spmv_hip_symmetric.h" // (spmv_hip_plan.h, spmv_hip_tuning.h, spmv_hip.h)
 #include "spmv_hip_multivec.h"
 #include "spmv_hip_transpose.h"
+#include "spmv_hip_f32values.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -133,6 +134,9 @@ public:
             A = load_csr(matrix_path, options, o, verbose);
             if (options.transpose_on_host)
                 A = transposed_on_host(A);
+            if (options.round_values_on_host)
+                for (auto & v : A.value)
+                    v = static_cast<double>(static_cast<float>(v));
             x = csr_matrix::value_array_type((std::size_t) A.columns, 1.0);
             y = csr_matrix::value_array_type((std::size_t) A.rows, 0.0);
         });
@@ -538,6 +542,53 @@ private:
     long long diagonal = 0;
 };
 
+// --f32-values: the values go to the device as 4-byte floats (no fp64 copy is kept there) and every run adds fl32(A) x to y, each
+// product and each sum in fp64
+class hip_csr_f32values_spmv_kernel : public hip_kernel_base
+{
+public:
+    using hip_kernel_base::hip_kernel_base;
+    void init(TraceConfig const &, std::ostream & o, bool verbose) override
+    {
+        auto const t0 = std::chrono::steady_clock::now();
+        guarded_init(matrix_path, [&] {
+            A = load_csr(matrix_path, options, o, verbose);
+            x.assign((std::size_t) A.columns, 1.0);
+            y.assign((std::size_t) A.rows, 0.0);
+        });
+        std::size_t const nnz = (std::size_t) A.row_ptr[(std::size_t) A.rows];
+        {
+            std::vector<float> narrow(nnz);
+            std::int64_t n = 0;
+            check(spmv_hip_narrow_values_host((std::int64_t) nnz, A.value.data(), narrow.data(), &n, &max_rounding), "narrow_values_host");
+            inexact = n;
+        }
+        auto const t1 = std::chrono::steady_clock::now();
+        if (options.num_gpus == 1)
+            options.num_gpus = 0; // --gpus 1: the one-device context this upload needs
+        create_context();
+        check(spmv_hip_upload_csr_f32values(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(), A.column_index.data(),
+                                            A.value.data(), options.f32_values == 2 ? 0 : 1), "upload_csr_f32values");
+        init_load_seconds = std::chrono::duration<double>(t1 - t0).count();
+        init_upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    }
+    std::string name() const override { return "hip-csr-spmv-f32values"; }
+    std::ostream & print(std::ostream & o) const override
+    {
+        print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
+        o << ",\n\"value_bytes\": 4,\n\"values_inexact\": " << inexact << ",\n\"max_value_rounding\": " << max_rounding;
+        return print_device(o) << "\n}";
+    }
+
+    double flops_per_run() const override { return 2.0 * A.num_entries; }
+    double bytes_per_run() const override { return 8.0 * A.row_ptr[(std::size_t) A.rows] + 4.0 * (A.rows + 1.0) + 16.0 * A.rows + 8.0 * A.columns; }
+
+private:
+    csr_matrix::Matrix A;
+    long long inexact = 0;
+    double max_rounding = 0.0;
+};
+
 // --transpose: A stays on the device as it is stored and every run adds A' x to y (x has rows entries, y has columns): no
 // transposed copy of the matrix is made, on the host or on the device
 class hip_csr_transposed_spmv_kernel : public hip_kernel_base
@@ -753,6 +804,7 @@ std::unique_ptr<Kernel> make_spmv_kernel(SpmvFormat format, bool hip, std::strin
         if (hip && opt.symmetric) return std::make_unique<hip_csr_symmetric_spmv_kernel>(path, opt);
         if (hip && opt.vectors > 0) return std::make_unique<hip_csr_multivec_spmv_kernel>(path, opt);
         if (hip && opt.transpose) return std::make_unique<hip_csr_transposed_spmv_kernel>(path, opt);
+        if (hip && opt.f32_values) return std::make_unique<hip_csr_f32values_spmv_kernel>(path, opt);
         if (hip) return std::make_unique<hip_csr_spmv_kernel>(path, opt);
         return std::make_unique<csr_spmv_kernel>(path, opt);
     case SpmvFormat::coo:

@@ -8,6 +8,8 @@
 //       No fallback: if the device library cannot run, init() throws kernel_error.
 //   hip_csr_symmetric_spmv_kernel (--symmetric)
 //       the stored triangle of a symmetric / skew-symmetric file multiplied as the whole matrix, each stored value read once.
+//   hip_csr_f32values_spmv_kernel (--f32-values)
+//       y += fl32(A) x: the values stored and streamed as 4-byte floats, products and sums in fp64 (hip-csr-spmv-f32values).
 //   hip_csr_transposed_spmv_kernel (--transpose)
 //       y += A' x from the CSR arrays of A as they are (x has rows entries, y has columns); no transposed copy is made.
 //
@@ -42,6 +44,11 @@ struct SpmvOptions
                                    // (hip-csr only: spmv_hip_upload_csr_symmetric, include/spmv_hip_symmetric.h)
     bool transpose = false;        // EXTENSION: y += A' x from the arrays of A as stored (hip-csr, one device:
                                    // spmv_hip_upload_csr_transposed, include/spmv_hip_transpose.h)
+    int f32_values = 0;            // EXTENSION: 1 = the values are stored and streamed as 4-byte floats, rounded where they must be
+                                   // (--f32-values, --f32-values=round); 2 = values that are not floats already are refused
+                                   // (--f32-values=exact): hip-csr, one device (spmv_hip_upload_csr_f32values, spmv_hip_f32values.h)
+    bool round_values_on_host = false; // the CPU CSR kernel multiplies the values rounded by static_cast<float>: what --check
+                                   // compares --f32-values with (set by the program, not by an option)
     bool transpose_on_host = false; // the CPU CSR kernel multiplies the matrix transposed on the host: what --check compares
                                    // --transpose with (set by the program, not by an option)
     int vectors = 0;               // EXTENSION: > 0: Y += A X for that many vectors (hip-csr, one device: include/spmv_hip_multivec.h)

@@ -1,5 +1,5 @@
-"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h and
-spmv_hip_transpose.h (the C ABI of libspmv_hip.so).
+"""ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
+spmv_hip_transpose.h and spmv_hip_f32values.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -19,11 +19,11 @@ if os.environ.get("SPMV_HIP_EXPERIMENTS") == "1":
 elif os.environ.get("SPMV_HIP_EXPERIMENTS", "").endswith(".so"):  # an ablation build of tools/ablate.sh
     LIB_PATH = os.path.abspath(os.environ["SPMV_HIP_EXPERIMENTS"])
 # the drop-in boundary (what an adapter of the reference binds) and the headers that include it (tuning switches; Level 2;
-# the symmetric multiply of a stored triangle; Y += A X for several vectors; y += A' x)
+# the symmetric multiply of a stored triangle; Y += A X for several vectors; y += A' x; values stored as floats)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
-                                          "spmv_hip_transpose.h")]
+                                          "spmv_hip_transpose.h", "spmv_hip_f32values.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -129,6 +129,14 @@ SIGNATURES = {
     "spmv_hip_csr_spmv_t": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_tr_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
     "spmv_hip_tr_plan_destroy": (None, [_vp]),
+    "spmv_hip_narrow_values_host": (C.c_int, [C.c_int64, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "spmv_hip_f32_plan_preview": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_uint, _vp, C.c_int, _vp, C.c_int64]),
+    "spmv_hip_narrow_values": (C.c_int, [C.c_int64, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), _vp]),
+    "spmv_hip_f32_plan_csr": (C.c_int, [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, C.c_uint, _vp]),
+    "spmv_hip_csr_spmv_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_f32_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
+    "spmv_hip_f32_plan_destroy": (None, [_vp]),
+    "spmv_hip_upload_csr_f32values": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
 }
 
 
@@ -304,6 +312,18 @@ class Context:
             col, val = _EMPTY_I32, _EMPTY_F64
         check(self.lib.spmv_hip_upload_csr_transposed(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data))
         self.rows, self.cols = cols, rows  # of the operator that runs, A'
+
+    def upload_csr_f32values(self, rows, cols, row_ptr, col, val, allow_rounding=True):
+        """A with its fp64 values narrowed to floats on the way to the device (no fp64 copy is kept): runs then add fl32(A) x
+        to y, every product and sum in fp64.  allow_rounding=False refuses values that are not floats already
+        (include/spmv_hip_f32values.h)."""
+        row_ptr, col, val = _i32(row_ptr), _i32(col), _f64(val)
+        nnz = int(row_ptr[rows]) if len(row_ptr) > rows >= 0 else -1
+        if len(col) == 0:
+            col, val = _EMPTY_I32, _EMPTY_F64
+        check(self.lib.spmv_hip_upload_csr_f32values(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data,
+                                                     1 if allow_rounding else 0))
+        self.rows, self.cols = rows, cols
 
     def set_x(self, x):
         x = _f64(x)
@@ -568,6 +588,89 @@ class TrPlan:
     def spmv_t(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
         """y += A' x; raw device addresses, d_x (rows entries) != d_y (cols entries)."""
         check(self.lib.spmv_hip_csr_spmv_t(self.h, d_row_ptr, d_col, d_val, d_x, d_y, stream))
+
+
+F32_INFO_KEYS = ["rows", "cols", "stored_entries", "tiles", "long_row_tiles", "longest_row", "flags", "device_bytes",
+                 "streamed_bytes", "uniform_tiles", "scalar_tiles", "workgroups"]
+F32_TILE, F32_TILE_ROWS = 512, 64
+
+
+def narrow_values_host(value):
+    """(float32 array, inexact count, largest relative change) of spmv_hip_narrow_values_host; ERR_OVERFLOW raises."""
+    value = _f64(value)
+    out = np.zeros(max(1, len(value)), dtype=np.float32)
+    inexact, rel = C.c_int64(-1), C.c_double(-1.0)
+    check(load().spmv_hip_narrow_values_host(len(value), value.ctypes.data if len(value) else None, out.ctypes.data,
+                                             C.byref(inexact), C.byref(rel)))
+    return out[:len(value)], inexact.value, rel.value
+
+
+def f32_plan_preview(rows, cols, row_ptr, flags=0, table=True):
+    """What F32Plan would choose for this HOST row_ptr, without a device: (info dict, tile table).  The table is an int32
+    array [tiles, 4] of {first row, first entry, rows, lanes_log2} in launch order, or None with table=False."""
+    lib = load()
+    row_ptr = _i32(row_ptr)
+    if len(row_ptr) < rows + 1:
+        raise ValueError("row_ptr needs rows + 1 entries")
+    out = np.zeros(len(F32_INFO_KEYS), dtype=np.int64)
+    check(lib.spmv_hip_f32_plan_preview(rows, cols, row_ptr.ctypes.data, flags, out.ctypes.data, len(out), None, 0))
+    info = dict(zip(F32_INFO_KEYS, out.tolist()))
+    if not table:
+        return info, None
+    tab = np.zeros((info["tiles"], 4), dtype=np.int32)
+    check(lib.spmv_hip_f32_plan_preview(rows, cols, row_ptr.ctypes.data, flags, out.ctypes.data, len(out),
+                                        tab.ctypes.data if tab.size else None, tab.size))
+    return info, tab
+
+
+class F32Plan:
+    """Level-2 plan of y += fl32(A) x over the caller's FLOAT value array (spmv_hip_f32_plan_*): host row_ptr only."""
+
+    INFO_KEYS = F32_INFO_KEYS
+
+    def __init__(self, rows, cols, host_row_ptr, flags=0, stream=0):
+        self.lib = load()
+        self.h = None
+        rp = _i32(host_row_ptr)
+        if len(rp) < rows + 1:
+            raise ValueError("host_row_ptr needs rows + 1 entries")
+        h = _vp()
+        check(self.lib.spmv_hip_f32_plan_csr(C.byref(h), rows, cols, rp.ctypes.data, flags, stream))
+        self.h = h
+        self.rows, self.cols = rows, cols
+
+    def close(self):
+        if self.h:
+            self.lib.spmv_hip_f32_plan_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.int64)
+        check(self.lib.spmv_hip_f32_plan_info(self.h, out, len(out)))
+        return dict(zip(self.INFO_KEYS, out.tolist()))
+
+    def spmv(self, d_row_ptr, d_col, d_val32, d_x, d_y, stream=0):
+        """y += fl32(A) x; raw device addresses, d_val32 a float array, d_x != d_y."""
+        check(self.lib.spmv_hip_csr_spmv_f32(self.h, d_row_ptr, d_col, d_val32, d_x, d_y, stream))
+
+
+def narrow_values(n, d_value, d_out, stream=0):
+    """(inexact count, largest relative change) of spmv_hip_narrow_values on device arrays (raw addresses)."""
+    inexact, rel = C.c_int64(-1), C.c_double(-1.0)
+    check(load().spmv_hip_narrow_values(n, d_value, d_out, C.byref(inexact), C.byref(rel), stream))
+    return inexact.value, rel.value
 
 
 def _dev(a):
