@@ -1,0 +1,464 @@
+// compact.hip -- include/spmv_hip_compact.h: y += fl32(A) x with the columns of a tile as 16-bit codes (a 3-bit window number and
+// a 13-bit offset from one of eight per-tile bases).  The tiles are those of f32values.hip, asked from spmv_hip_f32_plan_preview
+// so that the two tables cannot drift apart; the bases and the codes are made on the host by a few threads, tile by tile; the
+// kernel is csr_compact.hpp.
+#include "internal.hpp"
+#include "csr_compact.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <atomic>
+#include <new>
+#include <system_error>
+#include <thread>
+
+using namespace spmvi;
+
+struct spmv_hip_c16_plan {
+    int32_t rows = 0, cols = 0, nnz = 0;
+    unsigned flags = 0;
+    int ntiles = 0, compact_tiles = 0, wide_tiles = 0, long_tiles = 0;
+    long long compact_entries = 0, streamed_bytes = 0;
+    long long windows_hist[SPMV_HIP_C16_WINDOWS] = {0};
+    size_t device_bytes = 0;
+    // one allocation: descriptors (ntiles + 1), bases (8 per tile), codes
+    char * d_all = nullptr;
+    const int4 * d_desc = nullptr;
+    const int * d_bases = nullptr;
+    const uint16_t * d_codes = nullptr;
+};
+
+namespace {
+
+struct HostPlan {
+    spmv_hip_c16_plan numbers;
+    std::vector<int4> desc;
+    std::vector<int32_t> bases;    // 8 per tile
+    std::vector<int32_t> windows;  // per tile, 0 = wide
+    std::vector<uint16_t> by_entry; // nnz codes by entry index (0 in wide tiles)
+    std::vector<uint16_t> codes;   // the device layout: a compact tile's codes from a quad of its own
+};
+
+// window bases and codes of the entries [k0, k1); returns the windows needed (more than 8: nothing is written)
+int code_tile(const int32_t * col, int32_t k0, int32_t k1, int32_t * base, uint16_t * code, std::vector<int32_t> & sorted)
+{
+    if (k1 == k0) {
+        std::fill(base, base + SPMV_HIP_C16_WINDOWS, 0);
+        return 1;
+    }
+    sorted.assign(col + k0, col + k1);
+    if (!std::is_sorted(sorted.begin(), sorted.end()))
+        std::sort(sorted.begin(), sorted.end());
+    int32_t b[SPMV_HIP_C16_WINDOWS];
+    int nw = 1;
+    b[0] = sorted[0];
+    for (int32_t c : sorted)
+        if ((long long) c >= (long long) b[nw - 1] + SPMV_HIP_C16_WINDOW_SPAN) {
+            if (nw == SPMV_HIP_C16_WINDOWS)
+                return nw + 1;
+            b[nw++] = c;
+        }
+    for (int w = 0; w < SPMV_HIP_C16_WINDOWS; ++w)
+        base[w] = b[w < nw ? w : nw - 1];
+    for (int32_t k = k0; k < k1; ++k) {
+        int w = nw - 1;
+        while (col[k] < b[w])
+            --w;
+        code[k] = (uint16_t) ((w << spmv::kC16OffsetBits) | (col[k] - b[w]));
+    }
+    return nw;
+}
+
+int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, const int32_t * col, unsigned flags)
+{
+    spmv_hip_c16_plan & pl = hp.numbers;
+    if (rows < 0 || !p)
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
+    // the tiles of the fp32-value plan in one call (it validates cols, row_ptr and the flags): a tile holds at least one row
+    int64_t fi[SPMV_HIP_F32_INFO] = {0};
+    std::vector<int32_t> tab(4 * (size_t) rows);
+    int rc = spmv_hip_f32_plan_preview(rows, cols, p, flags, fi, SPMV_HIP_F32_INFO, tab.data(), (int64_t) tab.size());
+    if (rc != 0)
+        return rc;
+    const int32_t nnz = p[rows];
+    pl.rows = rows;
+    pl.cols = cols;
+    pl.nnz = nnz;
+    pl.flags = flags;
+    if (nnz > 0 && !col)
+        return fail(SPMV_HIP_ERR_INVALID, "host_column_index is null");
+    bool bad = false;
+    for (int32_t e = 0; e < nnz; ++e)
+        bad |= col[e] < 0 || col[e] >= cols;
+    if (bad)
+        return fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)");
+    const int nt = (int) fi[3];
+    if (nt == 0)
+        return SPMV_HIP_OK; // the multiply does nothing
+    pl.ntiles = nt;
+    pl.long_tiles = (int) fi[4];
+    hp.desc.resize((size_t) nt + 1);
+    hp.bases.assign(8 * (size_t) nt, 0);
+    hp.windows.assign((size_t) nt, 0);
+    hp.by_entry.assign((size_t) nnz, 0);
+    // the bases and the codes, tile by tile, on a few host threads
+    const int threads = (int) std::max(1u, std::min({8u, std::thread::hardware_concurrency(), (unsigned) (nt / 4096 + 1)}));
+    std::atomic<bool> out_of_memory{false};
+    auto work = [&](int t) { // (nothing may be thrown out of a thread: a worker's bad_alloc is reported below)
+        try {
+            std::vector<int32_t> sorted;
+            for (int w = (int) ((long long) nt * t / threads), w1 = (int) ((long long) nt * (t + 1) / threads); w < w1; ++w) {
+                const int32_t r = tab[4 * (size_t) w], k0 = tab[4 * (size_t) w + 1], k1 = p[r + tab[4 * (size_t) w + 2]];
+                const int nw = code_tile(col, k0, k1, &hp.bases[8 * (size_t) w], hp.by_entry.data(), sorted);
+                hp.windows[(size_t) w] = nw <= SPMV_HIP_C16_WINDOWS ? nw : 0;
+            }
+        } catch (std::bad_alloc const &) {
+            out_of_memory = true;
+        }
+    };
+    {
+        std::vector<std::thread> pool;
+        int t = 1;
+        try {
+            pool.reserve((size_t) threads);
+            for (; t < threads; ++t)
+                pool.emplace_back(work, t);
+        } catch (std::system_error const &) { // no more threads to be had: this thread does the parts that were not started
+        } catch (std::bad_alloc const &) {
+            out_of_memory = true;
+        }
+        work(0);
+        for (; t < threads; ++t)
+            work(t);
+        for (auto & th : pool)
+            th.join();
+    }
+    if (out_of_memory)
+        return fail(SPMV_HIP_ERR_ALLOC, "compact plan: host memory");
+    // the descriptors (the meta word of f32values.hip's, rebuilt from its tile table) and the device layout of the codes
+    long long quads = 0, row_ptr_bytes = 0;
+    int uniform_tiles = 0, scalar_tiles = 0;
+    for (int w = 0; w < nt; ++w) {
+        const int32_t r = tab[4 * (size_t) w], k0 = tab[4 * (size_t) w + 1], nr = tab[4 * (size_t) w + 2], ll = tab[4 * (size_t) w + 3];
+        const int32_t k1 = p[r + nr], kb = k0 & ~3;
+        const int nw = hp.windows[(size_t) w];
+        int meta;
+        if (nr == 1 && (long long) k1 - kb > spmv::kF32Tile) {
+            meta = std::min(k1 - k0, 0xFFFF) | (ll << spmv::kTileMetaLanesShift);
+        } else {
+            int maxlen = 0, minlen = INT32_MAX;
+            for (int32_t i = r; i < r + nr; ++i) {
+                maxlen = std::max(maxlen, p[i + 1] - p[i]);
+                minlen = std::min(minlen, p[i + 1] - p[i]);
+            }
+            const bool fast = k1 > k0 && (long long) ((k1 - 1) & ~3) + 4 <= nnz;
+            const bool uniform = fast && minlen == maxlen;
+            meta = maxlen | (ll << spmv::kTileMetaLanesShift) | (fast ? spmv::kTileMetaFast : 0) | (uniform ? spmv::kTileMetaUniform : 0);
+            if (!uniform)
+                row_ptr_bytes += 4LL * (nr + 1);
+            uniform_tiles += uniform;
+            scalar_tiles += !fast;
+        }
+        unsigned quad = 0;
+        if (nw > 0) {
+            meta |= spmv::kC16MetaCompact | (nw == 1 ? spmv::kC16MetaOneWindow : 0);
+            if (quads > 0xFFFFFFFFLL)
+                return fail(SPMV_HIP_ERR_OVERFLOW, "the code stream is too long for a 32-bit quad index");
+            quad = (unsigned) quads;
+            if (k1 > k0)
+                quads += ((k1 - 1 - kb) >> 2) + 1;
+            ++pl.compact_tiles;
+            pl.compact_entries += k1 - k0;
+            ++pl.windows_hist[nw - 1];
+        } else {
+            ++pl.wide_tiles;
+        }
+        hp.desc[(size_t) w] = make_int4(r, k0, meta, (int) quad);
+    }
+    hp.desc[(size_t) nt] = make_int4(rows, nnz, 0, 0);
+    // the meta words are f32values.hip's rule restated: its own counts of them say whether the two have drifted apart
+    if (uniform_tiles != fi[9] || scalar_tiles != fi[10] ||
+        8LL * nnz + row_ptr_bytes + 16LL * rows + 8LL * cols + 16LL * (nt + 1) != fi[8])
+        return fail(SPMV_HIP_ERR_STATE, "compact plan: the tile kinds differ from the fp32-value plan's (an internal error)");
+    hp.codes.assign(4 * (size_t) quads, 0);
+    for (int w = 0; w < nt; ++w)
+        if (hp.windows[(size_t) w] > 0) {
+            const int32_t k0 = hp.desc[(size_t) w].y, k1 = hp.desc[(size_t) w + 1].y;
+            if (k1 > k0)
+                std::memcpy(&hp.codes[4 * (size_t) (unsigned) hp.desc[(size_t) w].w + (size_t) (k0 & 3)], &hp.by_entry[(size_t) k0],
+                            (size_t) (k1 - k0) * sizeof(uint16_t));
+        }
+    pl.device_bytes = (16 * ((size_t) nt + 1) + 32 * (size_t) nt + 8 * (size_t) quads + 15) & ~(size_t) 15;
+    pl.streamed_bytes = 6LL * pl.compact_entries + 8LL * (nnz - pl.compact_entries) + row_ptr_bytes + 16LL * rows + 8LL * cols +
+                        16LL * (nt + 1) + 32LL * nt;
+    return SPMV_HIP_OK;
+}
+
+int plan_host_guarded(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, const int32_t * col, unsigned flags)
+{
+    try {
+        return plan_host(hp, rows, cols, p, col, flags);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "compact plan: host memory");
+    }
+}
+
+void plan_numbers(const spmv_hip_c16_plan & pl, int64_t * out, int n)
+{
+    int64_t v[SPMV_HIP_C16_INFO] = {pl.rows, pl.cols, pl.nnz, pl.flags, (pl.ntiles + 3) / 4, pl.ntiles, pl.compact_tiles, pl.wide_tiles,
+                                    pl.long_tiles, pl.compact_entries};
+    for (int w = 0; w < SPMV_HIP_C16_WINDOWS; ++w)
+        v[10 + w] = pl.windows_hist[w];
+    v[18] = (int64_t) pl.device_bytes;
+    v[19] = pl.streamed_bytes;
+    for (int i = 0; i < n && i < SPMV_HIP_C16_INFO; ++i)
+        out[i] = v[i];
+}
+
+// the host plan onto the current device
+int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
+{
+    spmv_hip_c16_plan * pl = new (std::nothrow) spmv_hip_c16_plan(hp.numbers);
+    if (!pl)
+        return fail(SPMV_HIP_ERR_ALLOC, "plan allocation failed");
+    if (pl->ntiles > 0) {
+        const size_t desc_bytes = hp.desc.size() * sizeof(int4), base_bytes = hp.bases.size() * sizeof(int32_t),
+                     code_bytes = hp.codes.size() * sizeof(uint16_t);
+        hipError_t e = hipMalloc((void **) &pl->d_all, pl->device_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(pl->d_all, hp.desc.data(), desc_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(pl->d_all + desc_bytes, hp.bases.data(), base_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && code_bytes > 0)
+            e = hipMemcpyAsync(pl->d_all + desc_bytes + base_bytes, hp.codes.data(), code_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            spmv_hip_c16_plan_destroy(pl);
+            return fail_hip(e, "compact plan: descriptors, bases and codes");
+        }
+        pl->d_desc = reinterpret_cast<const int4 *>(pl->d_all);
+        pl->d_bases = reinterpret_cast<const int *>(pl->d_all + desc_bytes);
+        pl->d_codes = reinterpret_cast<const uint16_t *>(pl->d_all + desc_bytes + base_bytes);
+    }
+    *out = pl;
+    return SPMV_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int spmv_hip_c16_plan_preview(int32_t rows, int32_t cols, const int32_t * host_row_ptr, const int32_t * host_column_index, unsigned flags,
+                              int64_t * out, int n, int32_t * tile_table, int64_t tile_table_ints, uint16_t * codes)
+{
+    if (!out || n < 0 || tile_table_ints < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "out is null, or a negative count");
+    HostPlan hp;
+    int rc = plan_host_guarded(hp, rows, cols, host_row_ptr, host_column_index, flags);
+    if (rc != 0)
+        return rc;
+    const int nt = hp.numbers.ntiles;
+    if (tile_table) {
+        if ((long long) SPMV_HIP_C16_TILE_INTS * nt > tile_table_ints)
+            return fail(SPMV_HIP_ERR_INVALID, "tile_table is too small: it takes 13 int32 values per tile");
+        for (int w = 0; w < nt; ++w) {
+            int32_t * t = tile_table + (size_t) SPMV_HIP_C16_TILE_INTS * w;
+            t[0] = hp.desc[(size_t) w].x;
+            t[1] = hp.desc[(size_t) w].y;
+            t[2] = hp.desc[(size_t) w + 1].x - hp.desc[(size_t) w].x;
+            t[3] = (hp.desc[(size_t) w].z >> spmv::kTileMetaLanesShift) & 7;
+            t[4] = hp.windows[(size_t) w];
+            for (int b = 0; b < 8; ++b)
+                t[5 + b] = t[4] ? hp.bases[8 * (size_t) w + b] : 0;
+        }
+    }
+    if (codes && hp.numbers.nnz > 0) {
+        if (hp.by_entry.empty())
+            std::memset(codes, 0, (size_t) hp.numbers.nnz * sizeof(uint16_t)); // (rows or cols of zero cannot have entries: not reached)
+        else
+            std::memcpy(codes, hp.by_entry.data(), hp.by_entry.size() * sizeof(uint16_t));
+    }
+    plan_numbers(hp.numbers, out, n);
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_c16_plan_csr(spmv_hip_c16_plan ** plan, int32_t rows, int32_t cols, const int32_t * host_row_ptr,
+                          const int32_t * host_column_index, unsigned flags, void * stream)
+{
+    if (!plan)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    *plan = nullptr;
+    HostPlan hp;
+    int rc = plan_host_guarded(hp, rows, cols, host_row_ptr, host_column_index, flags);
+    if (rc != 0)
+        return rc;
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1)
+        return fail(SPMV_HIP_ERR_NO_DEVICE, "no HIP device visible");
+    return build_plan(plan, hp, static_cast<hipStream_t>(stream));
+}
+
+int spmv_hip_csr_spmv_c16(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                          const double * d_x, double * d_y, void * stream)
+{
+    if (!pl)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    if (d_x && (const void *) d_x == (const void *) d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
+    if (pl->ntiles == 0) // rows, cols or nnz of zero
+        return SPMV_HIP_OK;
+    if (!d_row_ptr || !d_value || !d_x || !d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
+    if (!d_column_index && pl->wide_tiles > 0)
+        return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null and the plan has wide tiles, which read the 32-bit columns");
+    if (!aligned16(d_column_index) || !aligned16(d_value))
+        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
+    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
+    if ((long long) pl->cols * 8 < (1LL << 32))
+        hipLaunchKernelGGL(spmv::csr_compact_kernel<true>, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr,
+                           d_column_index, d_value, d_x, d_y, exact);
+    else
+        hipLaunchKernelGGL(spmv::csr_compact_kernel<false>, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr,
+                           d_column_index, d_value, d_x, d_y, exact);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_c16_plan_verify(const spmv_hip_c16_plan * pl, const int32_t * d_column_index, int64_t * mismatches, void * stream)
+{
+    if (!pl || !mismatches)
+        return fail(SPMV_HIP_ERR_INVALID, "plan / mismatches null");
+    *mismatches = 0;
+    if (pl->ntiles == 0)
+        return SPMV_HIP_OK;
+    if (!d_column_index)
+        return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned long long * d_count = nullptr, count = 0;
+    HIP_TRY(hipMalloc((void **) &d_count, sizeof count));
+    hipError_t e = hipMemsetAsync(d_count, 0, sizeof count, s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(spmv::c16_verify_kernel, dim3((unsigned) ((pl->ntiles + 3) / 4)), dim3(256), 0, s, pl->ntiles, pl->d_desc,
+                           pl->d_bases, pl->d_codes, d_column_index, d_count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    (void) hipFree(d_count);
+    if (e != hipSuccess)
+        return fail_hip(e, "c16_plan_verify");
+    *mismatches = (int64_t) count;
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_c16_plan_info(const spmv_hip_c16_plan * pl, int64_t * out, int n)
+{
+    if (!pl || !out || n < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "plan/out null");
+    plan_numbers(*pl, out, n);
+    return SPMV_HIP_OK;
+}
+
+void spmv_hip_c16_plan_destroy(spmv_hip_c16_plan * pl)
+{
+    if (!pl)
+        return;
+    if (pl->d_all)
+        (void) hipFree(pl->d_all);
+    delete pl;
+}
+
+// ---- Level 1 --------------------------------------------------------------------------------------------------------------------
+
+int spmv_hip_upload_csr_compact(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
+                                const int32_t * column_index, const double * value, int allow_rounding)
+{
+    if (!c)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
+    if (c->multi)
+        return fail(SPMV_HIP_ERR_STATE, "the compact multiply runs on one device (a context of spmv_hip_create)");
+    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
+    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
+    // everything that can refuse the matrix happens before anything is freed or copied
+    int64_t none = 0;
+    int rc = spmv_hip_f32_plan_preview(rows, cols, row_ptr, flags, &none, 0, nullptr, 0); // (row_ptr and the flags are checked here)
+    if (rc != 0)
+        return rc;
+    if (row_ptr[rows] != nnz)
+        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
+    HostPlan hp;
+    if ((rc = plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0) // (... the columns here)
+        return rc;
+    std::vector<float> narrow;
+    try {
+        narrow.resize((size_t) nnz);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "compact upload: host memory");
+    }
+    int64_t inexact = 0;
+    double max_rel = 0.0;
+    if ((rc = spmv_hip_narrow_values_host(nnz, value, narrow.data(), &inexact, &max_rel)) != 0)
+        return rc;
+    if (inexact > 0 && !allow_rounding) {
+        int64_t first = 0;
+        while (first < nnz && !((double) narrow[(size_t) first] != value[first] && value[first] == value[first]))
+            ++first;
+        char text[200];
+        std::snprintf(text, sizeof text, "%lld value(s) are not floats (the first is entry %lld, relative change at most %.3g) and allow_rounding is 0",
+                      (long long) inexact, (long long) first, max_rel);
+        return fail(SPMV_HIP_ERR_INVALID, text);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_ctx_matrix(c);
+    if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
+        return rc;
+    c->rows = rows;
+    c->cols = cols;
+    c->nnz = nnz;
+    auto alloc = [&](void ** p, size_t bytes) -> int {
+        hipError_t e = hipMalloc(p, bytes + 64);
+        if (e != hipSuccess)
+            return fail_hip(e, "hipMalloc");
+        c->bytes += bytes + 64;
+        return SPMV_HIP_OK;
+    };
+    auto cleanup = [&](int code) {
+        std::string const why = last_error_text();
+        free_ctx_matrix(c);
+        set_last_error_text(why);
+        return code;
+    };
+    const bool keep_columns = c->c16_plan->wide_tiles > 0; // only wide tiles read 32-bit columns
+    if ((rc = alloc((void **) &c->d_ptr, ((size_t) rows + 1) * sizeof(int32_t))) != 0 ||
+        (keep_columns && (rc = alloc((void **) &c->d_col, (size_t) nnz * sizeof(int32_t))) != 0) ||
+        (rc = alloc((void **) &c->d_val32, (size_t) nnz * sizeof(float))) != 0 ||
+        (rc = alloc((void **) &c->d_x, (size_t) cols * sizeof(double))) != 0 ||
+        (rc = alloc((void **) &c->d_y, (size_t) rows * sizeof(double))) != 0)
+        return cleanup(rc);
+    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, ((size_t) rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz > 0 && keep_columns)
+        e = hipMemcpyAsync(c->d_col, column_index, (size_t) nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz > 0)
+        e = hipMemcpyAsync(c->d_val32, narrow.data(), (size_t) nnz * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->d_x, 0, (size_t) cols * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->d_y, 0, (size_t) rows * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess)
+        return cleanup(fail_hip(e, "upload (host arrays -> device)"));
+    c->bytes += c->c16_plan->device_bytes;
+    c->format = 8;
+    return SPMV_HIP_OK;
+}
+
+} // extern "C"

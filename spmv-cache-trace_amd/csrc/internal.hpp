@@ -11,6 +11,7 @@
 //   multivec.hip     Y += A X for up to 16 vectors in one pass over a CSR matrix (spmv_hip_multivec.h)
 //   transpose.hip    y += A' x from the CSR arrays of A as they are (spmv_hip_transpose.h)
 //   f32values.hip    y += fl32(A) x with the values stored as 4-byte floats (spmv_hip_f32values.h)
+//   compact.hip      ... and the columns of a tile as 16-bit window codes (spmv_hip_compact.h)
 #pragma once
 
 #include "spmv_hip_plan.h"
@@ -18,6 +19,7 @@
 #include "spmv_hip_multivec.h"
 #include "spmv_hip_transpose.h"
 #include "spmv_hip_f32values.h"
+#include "spmv_hip_compact.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -200,7 +202,8 @@ struct spmv_hip_ctx {
     bool timed = false;
     int format = 0; // 0 none, 1 csr, 2 coo, 3 ell, 4 hybrid (ell + coo remainder), 5 stored triangle of a (skew-)symmetric matrix,
                     // 6 csr multiplied transposed (rows / cols are those of the operator that runs, A'),
-                    // 7 csr with the values as 4-byte floats (d_val32; no fp64 values are kept)
+                    // 7 csr with the values as 4-byte floats (d_val32; no fp64 values are kept),
+                    // 8 ... and 16-bit column codes in the plan (d_col only where the plan has wide tiles)
     int32_t rows = 0, cols = 0, nnz = 0, row_length = 0, nnz2 = 0;
     int csr_algorithm = SPMV_HIP_CSR_AUTO;
     int csr_lanes = 0;
@@ -209,6 +212,7 @@ struct spmv_hip_ctx {
     spmv_hip_tr_plan * tr_plan = nullptr;   // format 6 (transpose.hip)
     spmv_hip_f32_plan * f32_plan = nullptr; // format 7 (f32values.hip)
     float * d_val32 = nullptr;              // ... its values
+    spmv_hip_c16_plan * c16_plan = nullptr; // format 8 (compact.hip; its values are d_val32 too)
     // block vectors of spmv_hip_run_block (multivec.hip; format 1 only): X (cols x block_k) and Y (rows x block_k), row-major,
     // apart from d_x / d_y; the plan is made on the first run_block after the matrix or k changed
     spmv_hip_mv_plan * mv_plan = nullptr;

@@ -97,6 +97,7 @@ enum Key
     key_vectors,
     key_transpose,
     key_f32_values,
+    key_compact,
 };
 
 bool parse_count(char const * arg, long long & out)
@@ -213,9 +214,34 @@ error_t parse_option(int key, char * arg, argp_state * state)
         else if (!std::strcmp(arg, "exact")) a.spmv.f32_values = 2;
         else argp_error(state, "f32-values: expected 'round' (the default) or 'exact'");
         break;
+    case key_compact:
+        if (!arg || !std::strcmp(arg, "round")) a.spmv.compact = 1;
+        else if (!std::strcmp(arg, "exact")) a.spmv.compact = 2;
+        else argp_error(state, "compact: expected 'round' (the default) or 'exact'");
+        break;
     case ARGP_KEY_END:
         if (a.list_perf_events)
             break;
+        if (a.spmv.compact) {
+            // what --compact runs on: hip-csr on one device (include/spmv_hip_compact.h); anything else is refused here rather
+            // than multiplied some other way
+            if (a.spmv.symmetric)
+                argp_error(state, "--compact cannot be combined with --symmetric: there is no symmetric kernel over 16-bit column codes");
+            if (a.spmv.transpose)
+                argp_error(state, "--compact cannot be combined with --transpose: there is no transposed kernel over 16-bit column codes");
+            if (a.spmv.vectors > 0)
+                argp_error(state, "--compact cannot be combined with --vectors: there is no multi-vector kernel over 16-bit column codes");
+            if (a.spmv.f32_values)
+                argp_error(state, "--compact cannot be combined with --f32-values: --compact stores the values as floats already "
+                                  "(--compact=exact refuses values that are not floats)");
+            if (a.kernel_type != KernelType::spmv || a.format != SpmvFormat::csr)
+                argp_error(state, "--compact needs the CSR kernel on the GPU (--spmv-format hip-csr or --csr PATH): "
+                                  "there is no COO, ELLPACK or hybrid kernel over 16-bit column codes");
+            if (!a.hip && (!a.shortcut || a.device_given))
+                argp_error(state, "--compact runs on the GPU only (--spmv-format hip-csr or --device hip): there is no CPU kernel over 16-bit column codes");
+            if (a.spmv.num_gpus > 1)
+                argp_error(state, "--compact runs on one device (--gpus must be 1)");
+        }
         if (a.spmv.f32_values) {
             // what --f32-values runs on: hip-csr on one device (include/spmv_hip_f32values.h); anything else is refused here rather
             // than multiplied some other way
@@ -376,6 +402,11 @@ int main(int argc, char ** argv)
          "(8 instead of 12 bytes per stored entry).  round (default): values are rounded to the nearest float and the JSON "
          "document says how many and by how much; exact: a matrix with values that are not floats already is refused.  --check "
          "compares with the CPU CSR kernel on the values rounded on the host", 2},
+        {"compact", key_compact, "round|exact", OPTION_ARG_OPTIONAL,
+         "EXTENSION (hip-csr, one device): --f32-values with the columns of a tile streamed as 16-bit codes, a 3-bit window number "
+         "and a 13-bit offset from one of eight per-tile bases (6 instead of 8 bytes per stored entry); tiles that need more "
+         "than eight windows keep their 32-bit columns, and the JSON document counts both kinds.  round (default) and exact are "
+         "those of --f32-values.  --check compares with the CPU CSR kernel on the values rounded on the host", 2},
         {"vectors", key_vectors, "K", 0,
          "EXTENSION (hip-csr, one device): Y += A X for K = 1 ... 16 vectors in one multiply, every stored entry read once; column c "
          "of X is x scaled by c + 1.  Flops count 2 nnz K; --check compares every column with the CPU CSR kernel", 2},
@@ -468,7 +499,7 @@ int main(int argc, char ** argv)
         int count = 0;
         if (spmv_hip_device_count(&count) == 0 && count > 0)
             args.hip = true;
-        else if (!args.spmv.symmetric && args.spmv.vectors == 0 && !args.spmv.transpose && !args.spmv.f32_values) // (those fail below: nothing runs in their place)
+        else if (!args.spmv.symmetric && args.spmv.vectors == 0 && !args.spmv.transpose && !args.spmv.f32_values && !args.spmv.compact) // (those fail below: nothing runs in their place)
             std::cerr << "note: no usable HIP device: the CPU (OpenMP) kernel runs (--device hip makes this an error, --device cpu silences the note)\n";
     }
 
@@ -487,6 +518,12 @@ int main(int argc, char ** argv)
     if (args.spmv.f32_values && !args.hip) {
         std::cerr << "--f32-values: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU kernel over "
                      "float values (nothing runs in its place)\n";
+        return EXIT_FAILURE;
+    }
+
+    if (args.spmv.compact && !args.hip) {
+        std::cerr << "--compact: the kernel would run on the CPU (no usable HIP device, or SPMV_DEVICE=cpu), and there is no CPU kernel over "
+                     "16-bit column codes (nothing runs in its place)\n";
         return EXIT_FAILURE;
     }
 
@@ -546,8 +583,9 @@ int main(int argc, char ** argv)
                 ref_options.transpose_on_host = true;
             }
             // (--f32-values: the values rounded on the host by static_cast<float> -- an independent path to the same operator)
-            if (args.spmv.f32_values) {
+            if (args.spmv.f32_values || args.spmv.compact) {
                 ref_options.f32_values = 0;
+                ref_options.compact = 0;
                 ref_options.round_values_on_host = true;
             }
             ref_options.vectors = 0;
@@ -579,7 +617,7 @@ int main(int argc, char ** argv)
             parity = ",\n\"parity\": {\"against\": \"csr-spmv (CPU, 1 thread)" +
                 std::string(args.spmv.symmetric ? " on the expanded matrix (expand_symmetry)" : "") +
                 std::string(args.spmv.transpose ? " on the matrix transposed on the host" : "") +
-                std::string(args.spmv.f32_values ? " on the values rounded to float on the host" : "") +
+                std::string(args.spmv.f32_values || args.spmv.compact ? " on the values rounded to float on the host" : "") +
                 (args.spmv.vectors > 0 ? ", every one of the " + std::to_string(k) + " columns" : std::string()) + ", " +
                 std::to_string(args.profile + 1) + " accumulating runs\", \"max_relative_error\": ";
             char buf[64];

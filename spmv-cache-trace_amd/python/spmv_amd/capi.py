@@ -1,5 +1,5 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
-spmv_hip_transpose.h and spmv_hip_f32values.h (the C ABI of libspmv_hip.so).
+spmv_hip_transpose.h, spmv_hip_f32values.h and spmv_hip_compact.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -19,11 +19,11 @@ if os.environ.get("SPMV_HIP_EXPERIMENTS") == "1":
 elif os.environ.get("SPMV_HIP_EXPERIMENTS", "").endswith(".so"):  # an ablation build of tools/ablate.sh
     LIB_PATH = os.path.abspath(os.environ["SPMV_HIP_EXPERIMENTS"])
 # the drop-in boundary (what an adapter of the reference binds) and the headers that include it (tuning switches; Level 2;
-# the symmetric multiply of a stored triangle; Y += A X for several vectors; y += A' x; values stored as floats)
+# the symmetric multiply of a stored triangle; Y += A X for several vectors; y += A' x; values stored as floats; ... with 16-bit column codes)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
-                                          "spmv_hip_transpose.h", "spmv_hip_f32values.h")]
+                                          "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -137,6 +137,13 @@ SIGNATURES = {
     "spmv_hip_f32_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
     "spmv_hip_f32_plan_destroy": (None, [_vp]),
     "spmv_hip_upload_csr_f32values": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
+    "spmv_hip_c16_plan_preview": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_uint, _vp, C.c_int, _vp, C.c_int64, _vp]),
+    "spmv_hip_c16_plan_csr": (C.c_int, [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, _vp, C.c_uint, _vp]),
+    "spmv_hip_csr_spmv_c16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_c16_plan_verify": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
+    "spmv_hip_c16_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
+    "spmv_hip_c16_plan_destroy": (None, [_vp]),
+    "spmv_hip_upload_csr_compact": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
 }
 
 
@@ -323,6 +330,17 @@ class Context:
             col, val = _EMPTY_I32, _EMPTY_F64
         check(self.lib.spmv_hip_upload_csr_f32values(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data,
                                                      1 if allow_rounding else 0))
+        self.rows, self.cols = rows, cols
+
+    def upload_csr_compact(self, rows, cols, row_ptr, col, val, allow_rounding=True):
+        """upload_csr_f32values with the columns of a tile as 16-bit window codes in the plan (6 bytes per stored entry): no fp64
+        values are kept and, where the plan has no wide tile, no 32-bit columns either (include/spmv_hip_compact.h)."""
+        row_ptr, col, val = _i32(row_ptr), _i32(col), _f64(val)
+        nnz = int(row_ptr[rows]) if len(row_ptr) > rows >= 0 else -1
+        if len(col) == 0:
+            col, val = _EMPTY_I32, _EMPTY_F64
+        check(self.lib.spmv_hip_upload_csr_compact(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data,
+                                                   1 if allow_rounding else 0))
         self.rows, self.cols = rows, cols
 
     def set_x(self, x):
@@ -664,6 +682,87 @@ class F32Plan:
     def spmv(self, d_row_ptr, d_col, d_val32, d_x, d_y, stream=0):
         """y += fl32(A) x; raw device addresses, d_val32 a float array, d_x != d_y."""
         check(self.lib.spmv_hip_csr_spmv_f32(self.h, d_row_ptr, d_col, d_val32, d_x, d_y, stream))
+
+
+C16_INFO_KEYS = ["rows", "cols", "stored_entries", "flags", "workgroups", "tiles", "compact_tiles", "wide_tiles", "long_row_tiles",
+                 "compact_entries"] + ["tiles_with_%d_windows" % w for w in range(1, 9)] + ["device_bytes", "streamed_bytes"]
+C16_WINDOWS, C16_WINDOW_SPAN, C16_TILE_INTS = 8, 8192, 13
+
+
+def c16_plan_preview(rows, cols, row_ptr, col, flags=0, table=True, codes=False):
+    """What C16Plan would choose for these HOST arrays, without a device: (info dict, tile table, codes).  The table is an
+    int32 array [tiles, 13] of {first row, first entry, rows, lanes_log2, windows (0 = wide), base[8]} in launch order (None
+    with table=False); codes the uint16 code of every stored entry by entry index, 0 in wide tiles (None with codes=False)."""
+    lib = load()
+    row_ptr, col = _i32(row_ptr), _i32(col)
+    if len(row_ptr) < rows + 1:
+        raise ValueError("row_ptr needs rows + 1 entries")
+    if rows >= 0 and len(col) < int(row_ptr[rows]):
+        raise ValueError("col needs row_ptr[rows] entries")
+    cp = col.ctypes.data if len(col) else None
+    out = np.zeros(len(C16_INFO_KEYS), dtype=np.int64)
+    check(lib.spmv_hip_c16_plan_preview(rows, cols, row_ptr.ctypes.data, cp, flags, out.ctypes.data, len(out), None, 0, None))
+    info = dict(zip(C16_INFO_KEYS, out.tolist()))
+    if not table and not codes:
+        return info, None, None
+    tab = np.zeros((info["tiles"], C16_TILE_INTS), dtype=np.int32)
+    cod = np.zeros(info["stored_entries"], dtype=np.uint16)
+    check(lib.spmv_hip_c16_plan_preview(rows, cols, row_ptr.ctypes.data, cp, flags, out.ctypes.data, len(out),
+                                        tab.ctypes.data if tab.size else None, tab.size,
+                                        cod.ctypes.data if codes and cod.size else None))
+    return info, (tab if table else None), (cod if codes else None)
+
+
+class C16Plan:
+    """Level-2 plan of y += fl32(A) x with 16-bit column codes (spmv_hip_c16_plan_*): host row_ptr and columns."""
+
+    INFO_KEYS = C16_INFO_KEYS
+
+    def __init__(self, rows, cols, host_row_ptr, host_col, flags=0, stream=0):
+        self.lib = load()
+        self.h = None
+        rp, col = _i32(host_row_ptr), _i32(host_col)
+        if len(rp) < rows + 1:
+            raise ValueError("host_row_ptr needs rows + 1 entries")
+        if rows >= 0 and len(col) < int(rp[rows]):
+            raise ValueError("host_col needs row_ptr[rows] entries")
+        h = _vp()
+        check(self.lib.spmv_hip_c16_plan_csr(C.byref(h), rows, cols, rp.ctypes.data, col.ctypes.data if len(col) else None, flags, stream))
+        self.h = h
+        self.rows, self.cols = rows, cols
+
+    def close(self):
+        if self.h:
+            self.lib.spmv_hip_c16_plan_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = np.zeros(len(self.INFO_KEYS), dtype=np.int64)
+        check(self.lib.spmv_hip_c16_plan_info(self.h, out, len(out)))
+        return dict(zip(self.INFO_KEYS, out.tolist()))
+
+    def spmv(self, d_row_ptr, d_col, d_val32, d_x, d_y, stream=0):
+        """y += fl32(A) x; raw device addresses, d_val32 a float array, d_x != d_y; d_col may be 0 / None where the plan has no
+        wide tile."""
+        check(self.lib.spmv_hip_csr_spmv_c16(self.h, d_row_ptr, d_col or None, d_val32, d_x, d_y, stream))
+
+    def verify(self, d_col, stream=0):
+        """How many entries of compact tiles decode to a column other than d_col's (the content guard)."""
+        n = C.c_int64(-1)
+        check(self.lib.spmv_hip_c16_plan_verify(self.h, d_col or None, C.byref(n), stream))
+        return n.value
 
 
 def narrow_values(n, d_value, d_out, stream=0):
