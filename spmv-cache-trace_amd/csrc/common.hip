@@ -30,6 +30,23 @@ int fail_hip(hipError_t e, const char * call)
     return SPMV_HIP_ERR_HIP;
 }
 
+int check_csr_row_ptr(int32_t rows, int32_t cols, const int32_t * rp)
+{
+    if (rows < 0 || cols < 0 || !rp)
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
+    return check_row_ptr_order(rows, rp);
+}
+
+int check_row_ptr_order(int32_t rows, const int32_t * rp)
+{
+    if (rp[0] != 0)
+        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[0] must be 0");
+    for (int32_t r = 0; r < rows; ++r)
+        if (rp[r + 1] < rp[r])
+            return fail(SPMV_HIP_ERR_INVALID, "row_ptr must be non-decreasing");
+    return SPMV_HIP_OK;
+}
+
 std::string last_error_text() { return g_last_error; }
 void set_last_error_text(std::string const & text) { g_last_error = text; }
 

@@ -1,17 +1,17 @@
 // compact.hip -- include/spmv_hip_compact.h: y += fl32(A) x with the columns of a tile as 16-bit codes (a 3-bit window number and
-// a 13-bit offset from one of eight per-tile bases).  The tiles are those of f32values.hip, asked from spmv_hip_f32_plan_preview
-// so that the two tables cannot drift apart; the bases and the codes are made on the host by a few threads, tile by tile; the
-// kernel is csr_compact.hpp.
-#include "internal.hpp"
+// a 13-bit offset from one of eight per-tile bases).  The tiles are f32values.hip's own (f32_plan.hpp): its descriptors as they
+// are, with the compact bits and the tile's first code quad added; the bases and the codes are made on the host by a few
+// threads, tile by tile; the kernel is csr_compact.hpp.
+#include "f32_plan.hpp"
 #include "csr_compact.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <atomic>
 #include <new>
 #include <system_error>
 #include <thread>
+#include <utility>
 
 using namespace spmvi;
 
@@ -73,14 +73,11 @@ int code_tile(const int32_t * col, int32_t k0, int32_t k1, int32_t * base, uint1
 int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, const int32_t * col, unsigned flags)
 {
     spmv_hip_c16_plan & pl = hp.numbers;
-    if (rows < 0 || !p)
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
-    // the tiles of the fp32-value plan in one call (it validates cols, row_ptr and the flags): a tile holds at least one row
-    int64_t fi[SPMV_HIP_F32_INFO] = {0};
-    std::vector<int32_t> tab(4 * (size_t) rows);
-    int rc = spmv_hip_f32_plan_preview(rows, cols, p, flags, fi, SPMV_HIP_F32_INFO, tab.data(), (int64_t) tab.size());
+    int rc = f32_check_host(rows, cols, p, flags);
     if (rc != 0)
         return rc;
+    F32HostPlan fp;
+    f32_plan_host(fp, rows, cols, p, flags);
     const int32_t nnz = p[rows];
     pl.rows = rows;
     pl.cols = cols;
@@ -93,12 +90,12 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
         bad |= col[e] < 0 || col[e] >= cols;
     if (bad)
         return fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)");
-    const int nt = (int) fi[3];
+    const int nt = fp.numbers.ntiles;
     if (nt == 0)
         return SPMV_HIP_OK; // the multiply does nothing
     pl.ntiles = nt;
-    pl.long_tiles = (int) fi[4];
-    hp.desc.resize((size_t) nt + 1);
+    pl.long_tiles = fp.numbers.long_tiles;
+    hp.desc = std::move(fp.desc); // nt + 1 records: tile w ends where tile w + 1 starts
     hp.bases.assign(8 * (size_t) nt, 0);
     hp.windows.assign((size_t) nt, 0);
     hp.by_entry.assign((size_t) nnz, 0);
@@ -109,8 +106,7 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
         try {
             std::vector<int32_t> sorted;
             for (int w = (int) ((long long) nt * t / threads), w1 = (int) ((long long) nt * (t + 1) / threads); w < w1; ++w) {
-                const int32_t r = tab[4 * (size_t) w], k0 = tab[4 * (size_t) w + 1], k1 = p[r + tab[4 * (size_t) w + 2]];
-                const int nw = code_tile(col, k0, k1, &hp.bases[8 * (size_t) w], hp.by_entry.data(), sorted);
+                const int nw = code_tile(col, hp.desc[(size_t) w].y, hp.desc[(size_t) w + 1].y, &hp.bases[8 * (size_t) w], hp.by_entry.data(), sorted);
                 hp.windows[(size_t) w] = nw <= SPMV_HIP_C16_WINDOWS ? nw : 0;
             }
         } catch (std::bad_alloc const &) {
@@ -136,51 +132,26 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
     }
     if (out_of_memory)
         return fail(SPMV_HIP_ERR_ALLOC, "compact plan: host memory");
-    // the descriptors (the meta word of f32values.hip's, rebuilt from its tile table) and the device layout of the codes
-    long long quads = 0, row_ptr_bytes = 0;
-    int uniform_tiles = 0, scalar_tiles = 0;
+    // the compact bits and the first code quad into the descriptors, and the device layout of the codes
+    long long quads = 0;
     for (int w = 0; w < nt; ++w) {
-        const int32_t r = tab[4 * (size_t) w], k0 = tab[4 * (size_t) w + 1], nr = tab[4 * (size_t) w + 2], ll = tab[4 * (size_t) w + 3];
-        const int32_t k1 = p[r + nr], kb = k0 & ~3;
+        int4 & d = hp.desc[(size_t) w];
+        const int32_t k0 = d.y, k1 = hp.desc[(size_t) w + 1].y, kb = k0 & ~3;
         const int nw = hp.windows[(size_t) w];
-        int meta;
-        if (nr == 1 && (long long) k1 - kb > spmv::kF32Tile) {
-            meta = std::min(k1 - k0, 0xFFFF) | (ll << spmv::kTileMetaLanesShift);
-        } else {
-            int maxlen = 0, minlen = INT32_MAX;
-            for (int32_t i = r; i < r + nr; ++i) {
-                maxlen = std::max(maxlen, p[i + 1] - p[i]);
-                minlen = std::min(minlen, p[i + 1] - p[i]);
-            }
-            const bool fast = k1 > k0 && (long long) ((k1 - 1) & ~3) + 4 <= nnz;
-            const bool uniform = fast && minlen == maxlen;
-            meta = maxlen | (ll << spmv::kTileMetaLanesShift) | (fast ? spmv::kTileMetaFast : 0) | (uniform ? spmv::kTileMetaUniform : 0);
-            if (!uniform)
-                row_ptr_bytes += 4LL * (nr + 1);
-            uniform_tiles += uniform;
-            scalar_tiles += !fast;
-        }
-        unsigned quad = 0;
-        if (nw > 0) {
-            meta |= spmv::kC16MetaCompact | (nw == 1 ? spmv::kC16MetaOneWindow : 0);
-            if (quads > 0xFFFFFFFFLL)
-                return fail(SPMV_HIP_ERR_OVERFLOW, "the code stream is too long for a 32-bit quad index");
-            quad = (unsigned) quads;
-            if (k1 > k0)
-                quads += ((k1 - 1 - kb) >> 2) + 1;
-            ++pl.compact_tiles;
-            pl.compact_entries += k1 - k0;
-            ++pl.windows_hist[nw - 1];
-        } else {
+        if (nw == 0) {
             ++pl.wide_tiles;
+            continue;
         }
-        hp.desc[(size_t) w] = make_int4(r, k0, meta, (int) quad);
+        if (quads > 0xFFFFFFFFLL)
+            return fail(SPMV_HIP_ERR_OVERFLOW, "the code stream is too long for a 32-bit quad index");
+        d.z |= spmv::kC16MetaCompact | (nw == 1 ? spmv::kC16MetaOneWindow : 0);
+        d.w = (int) (unsigned) quads;
+        if (k1 > k0)
+            quads += ((k1 - 1 - kb) >> 2) + 1;
+        ++pl.compact_tiles;
+        pl.compact_entries += k1 - k0;
+        ++pl.windows_hist[nw - 1];
     }
-    hp.desc[(size_t) nt] = make_int4(rows, nnz, 0, 0);
-    // the meta words are f32values.hip's rule restated: its own counts of them say whether the two have drifted apart
-    if (uniform_tiles != fi[9] || scalar_tiles != fi[10] ||
-        8LL * nnz + row_ptr_bytes + 16LL * rows + 8LL * cols + 16LL * (nt + 1) != fi[8])
-        return fail(SPMV_HIP_ERR_STATE, "compact plan: the tile kinds differ from the fp32-value plan's (an internal error)");
     hp.codes.assign(4 * (size_t) quads, 0);
     for (int w = 0; w < nt; ++w)
         if (hp.windows[(size_t) w] > 0) {
@@ -190,8 +161,8 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
                             (size_t) (k1 - k0) * sizeof(uint16_t));
         }
     pl.device_bytes = (16 * ((size_t) nt + 1) + 32 * (size_t) nt + 8 * (size_t) quads + 15) & ~(size_t) 15;
-    pl.streamed_bytes = 6LL * pl.compact_entries + 8LL * (nnz - pl.compact_entries) + row_ptr_bytes + 16LL * rows + 8LL * cols +
-                        16LL * (nt + 1) + 32LL * nt;
+    // the fp32-value plan's bytes with 2 instead of 4 bytes of column per compact entry, and the bases
+    pl.streamed_bytes = fp.numbers.streamed_bytes - 2LL * pl.compact_entries + 32LL * nt;
     return SPMV_HIP_OK;
 }
 
@@ -387,8 +358,7 @@ int spmv_hip_upload_csr_compact(spmv_hip_ctx * c, int32_t rows, int32_t cols, in
         return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
     const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
     // everything that can refuse the matrix happens before anything is freed or copied
-    int64_t none = 0;
-    int rc = spmv_hip_f32_plan_preview(rows, cols, row_ptr, flags, &none, 0, nullptr, 0); // (row_ptr and the flags are checked here)
+    int rc = f32_check_host(rows, cols, row_ptr, flags);
     if (rc != 0)
         return rc;
     if (row_ptr[rows] != nnz)
@@ -402,60 +372,20 @@ int spmv_hip_upload_csr_compact(spmv_hip_ctx * c, int32_t rows, int32_t cols, in
     } catch (std::bad_alloc const &) {
         return fail(SPMV_HIP_ERR_ALLOC, "compact upload: host memory");
     }
-    int64_t inexact = 0;
-    double max_rel = 0.0;
-    if ((rc = spmv_hip_narrow_values_host(nnz, value, narrow.data(), &inexact, &max_rel)) != 0)
+    if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
         return rc;
-    if (inexact > 0 && !allow_rounding) {
-        int64_t first = 0;
-        while (first < nnz && !((double) narrow[(size_t) first] != value[first] && value[first] == value[first]))
-            ++first;
-        char text[200];
-        std::snprintf(text, sizeof text, "%lld value(s) are not floats (the first is entry %lld, relative change at most %.3g) and allow_rounding is 0",
-                      (long long) inexact, (long long) first, max_rel);
-        return fail(SPMV_HIP_ERR_INVALID, text);
-    }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_ctx_matrix(c);
     if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
         return rc;
+    // only wide tiles read 32-bit columns
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr,
+                             column_index, c->c16_plan->wide_tiles > 0, narrow.data(), true)) != 0)
+        return rc;
     c->rows = rows;
     c->cols = cols;
     c->nnz = nnz;
-    auto alloc = [&](void ** p, size_t bytes) -> int {
-        hipError_t e = hipMalloc(p, bytes + 64);
-        if (e != hipSuccess)
-            return fail_hip(e, "hipMalloc");
-        c->bytes += bytes + 64;
-        return SPMV_HIP_OK;
-    };
-    auto cleanup = [&](int code) {
-        std::string const why = last_error_text();
-        free_ctx_matrix(c);
-        set_last_error_text(why);
-        return code;
-    };
-    const bool keep_columns = c->c16_plan->wide_tiles > 0; // only wide tiles read 32-bit columns
-    if ((rc = alloc((void **) &c->d_ptr, ((size_t) rows + 1) * sizeof(int32_t))) != 0 ||
-        (keep_columns && (rc = alloc((void **) &c->d_col, (size_t) nnz * sizeof(int32_t))) != 0) ||
-        (rc = alloc((void **) &c->d_val32, (size_t) nnz * sizeof(float))) != 0 ||
-        (rc = alloc((void **) &c->d_x, (size_t) cols * sizeof(double))) != 0 ||
-        (rc = alloc((void **) &c->d_y, (size_t) rows * sizeof(double))) != 0)
-        return cleanup(rc);
-    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, ((size_t) rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0 && keep_columns)
-        e = hipMemcpyAsync(c->d_col, column_index, (size_t) nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_val32, narrow.data(), (size_t) nnz * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_x, 0, (size_t) cols * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_y, 0, (size_t) rows * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-        return cleanup(fail_hip(e, "upload (host arrays -> device)"));
     c->bytes += c->c16_plan->device_bytes;
     c->format = 8;
     return SPMV_HIP_OK;

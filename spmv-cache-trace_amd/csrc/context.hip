@@ -84,6 +84,49 @@ int dev_alloc(spmv_hip_ctx * c, T ** out, size_t n)
     return SPMV_HIP_OK;
 }
 
+int csr_arrays_to_device(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr,
+                         const int32_t * column_index, bool keep_columns, const void * value, bool float_values)
+{
+    int rc;
+    if ((rc = dev_alloc(c, &c->d_ptr, nptr)) != 0 || (keep_columns && (rc = dev_alloc(c, &c->d_col, nnz)) != 0) ||
+        (rc = float_values ? dev_alloc(c, &c->d_val32, nnz) : dev_alloc(c, &c->d_val, nnz)) != 0 || (rc = dev_alloc(c, &c->d_x, nx)) != 0 ||
+        (rc = dev_alloc(c, &c->d_y, ny)) != 0)
+        return rc;
+    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, nptr * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz > 0 && keep_columns)
+        e = hipMemcpyAsync(c->d_col, column_index, nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz > 0)
+        e = float_values ? hipMemcpyAsync(c->d_val32, value, nnz * sizeof(float), hipMemcpyHostToDevice, c->stream)
+                         : hipMemcpyAsync(c->d_val, value, nnz * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->d_x, 0, nx * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->d_y, 0, ny * sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    return e == hipSuccess ? SPMV_HIP_OK : fail_hip(e, "upload (host arrays -> device)");
+}
+
+} // namespace
+
+namespace spmvi {
+
+int upload_ctx_csr(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr, const int32_t * column_index,
+                   bool keep_columns, const void * value, bool float_values)
+{
+    const int rc = csr_arrays_to_device(c, nptr, nx, ny, nnz, row_ptr, column_index, keep_columns, value, float_values);
+    if (rc != 0) {
+        std::string const why = last_error_text();
+        free_ctx_matrix(c);
+        set_last_error_text(why);
+    }
+    return rc;
+}
+
+} // namespace spmvi
+
+namespace {
+
 // ---- host arrays -> HBM beside the host tiler (round 5) ---------------------------------------------------------------------------
 // A copy from pageable host memory occupies the thread that issues it until the data has left (hipMemcpyAsync from pageable
 // memory is synchronous for the host), and Kernel::init used to do everything in a row: cut the tiles from row_ptr (11 ms for

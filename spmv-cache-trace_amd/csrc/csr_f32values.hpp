@@ -1,10 +1,16 @@
 // csr_f32values.hpp -- y += fl32(A) x (include/spmv_hip_f32values.h): the plain path of csr_wavetile_kernel with the value
 // stream at 4 bytes per entry.  A wave per tile of up to 512 entries counted from a 4-aligned entry, four waves per workgroup,
-// each with an LDS slice of its own; per lane and quad ONE 16-byte load of four columns and ONE 16-byte load of four floats,
-// both quads of a lane issued before anything waits; then the four x gathers, four widenings (v_cvt_f64_f32: exact, denormals
+// each with an LDS slice of its own; per lane and quad ONE load of four columns and ONE 16-byte load of four floats, both
+// quads of a lane issued before anything waits; then the four x gathers, four widenings (v_cvt_f64_f32: exact, denormals
 // included) and four fp64 multiplies, the rounded products parked in the slice and added up row by row by L lanes exactly as
 // the plain tile does (tile_common.hpp: tile_row_sum, group_sum).  No atomics anywhere: a row is written by one lane.
 // A row longer than a tile is a tile of its own: the whole wave in registers, 512 entries per step, one butterfly at the end.
+//
+// The tile is written once, f32_tile, over a COLUMN SOURCE: the only thing in which csr_f32values_kernel (32-bit columns,
+// WideColumns below) and csr_compact_kernel (16-bit window codes, csr_compact.hpp) differ.  A source says where the columns
+// of a quad come from -- load(o): the stored quad at offset o, columns(quad): its four column indices, at(k): the column at
+// offset k (WideColumns here, CodeColumns<ONE> there).  A kernel's SOURCE (WideSource here, CompactSource there) counts from
+// entry 0 and runs the two loops that read quads, quad_products and long_row_sum_f32, on the columns it chooses.
 #pragma once
 
 #include "tile_common.hpp"
@@ -19,28 +25,30 @@ constexpr int kF32TileRows = 64;
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // tile_products_wide's rules: lanes past the tile's end re-read its last quad; entries in front of the tile that share its
-// first quad are multiplied and never read back
-template <int QUADS, bool X32>
-__device__ __forceinline__ void tile_products_f32(double * prod, const int32_t * __restrict__ jt, const float * __restrict__ at,
-                                                  const double * __restrict__ x, int last, int lane)
+// first quad are multiplied and never read back.  cols and at count from the tile's first quad.  Every lane works out its
+// columns (the lanes past the tile's end hold its last quad's); only the gathers are predicated.
+template <int QUADS, bool X32, class Columns>
+__device__ __forceinline__ void quad_products(double * prod, const Columns cols, const float * __restrict__ at,
+                                              const double * __restrict__ x, int last, int lane)
 {
-    v4i c[QUADS];
+    typename Columns::quad c[QUADS];
     v4f v[QUADS];
 #pragma unroll
     for (int q = 0; q < QUADS; ++q) {
         int o = 256 * q + 4 * lane;
         o = o < last ? o : last;
-        c[q] = *reinterpret_cast<const v4i *>(jt + o);
+        c[q] = cols.load(o);
         v[q] = *reinterpret_cast<const v4f *>(at + o);
     }
 #pragma unroll
     for (int q = 0; q < QUADS; ++q) {
         const int o = 256 * q + 4 * lane;
+        const v4i j = cols.columns(c[q]);
         if (o <= last) {
-            const double q0 = (double) v[q].x * gather_x<X32>(x, c[q].x);
-            const double q1 = (double) v[q].y * gather_x<X32>(x, c[q].y);
-            const double q2 = (double) v[q].z * gather_x<X32>(x, c[q].z);
-            const double q3 = (double) v[q].w * gather_x<X32>(x, c[q].w);
+            const double q0 = (double) v[q].x * gather_x<X32>(x, j.x);
+            const double q1 = (double) v[q].y * gather_x<X32>(x, j.y);
+            const double q2 = (double) v[q].z * gather_x<X32>(x, j.z);
+            const double q3 = (double) v[q].w * gather_x<X32>(x, j.w);
             v2d * dst = reinterpret_cast<v2d *>(prod + o);
             dst[0] = v2d{q0, q1};
             dst[1] = v2d{q2, q3};
@@ -50,29 +58,30 @@ __device__ __forceinline__ void tile_products_f32(double * prod, const int32_t *
 
 // long_row_sum (tile_common.hpp) over float values: the 4-aligned interior [ka, kz) in quads, two per lane and step in
 // flight, four accumulators per lane; the up to three entries in front of ka and behind kz by single lanes.  Nothing is read
-// outside [k0, k1).
-template <bool X32>
-__device__ __forceinline__ double long_row_sum_f32(const int32_t * __restrict__ j, const float * __restrict__ a,
-                                                   const double * __restrict__ x, int k0, int k1, int lane)
+// outside [k0, k1).  cols and a count from entry 0.
+template <bool X32, class Columns>
+__device__ __forceinline__ double long_row_sum_f32(const Columns cols, const float * __restrict__ a, const double * __restrict__ x,
+                                                   int k0, int k1, int lane)
 {
     double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
     const int ka = (k0 + 3) & ~3, kz = k1 & ~3;
     if (ka >= kz) {
         for (int k = k0 + lane; k < k1; k += kWave)
-            z0 += (double) a[k] * x[j[k]];
+            z0 += (double) a[k] * x[cols.at(k)];
         return group_sum<kWave>(z0);
     }
     if (lane < ka - k0)
-        z0 += (double) a[k0 + lane] * x[j[k0 + lane]];
+        z0 += (double) a[k0 + lane] * x[cols.at(k0 + lane)];
     if (lane >= 4 && lane - 4 < k1 - kz)
-        z1 += (double) a[kz + lane - 4] * x[j[kz + lane - 4]];
+        z1 += (double) a[kz + lane - 4] * x[cols.at(kz + lane - 4)];
     for (int o = ka + 4 * lane; o < kz; o += 2 * 4 * kWave) {
         const bool two = o + 4 * kWave < kz;
         const int o2 = two ? o + 4 * kWave : o;
-        const v4i ca = *reinterpret_cast<const v4i *>(j + o), cb = *reinterpret_cast<const v4i *>(j + o2);
+        const typename Columns::quad ca = cols.load(o), cb = cols.load(o2);
         const v4f va = *reinterpret_cast<const v4f *>(a + o), vb = *reinterpret_cast<const v4f *>(a + o2);
-        const double xa0 = gather_x<X32>(x, ca.x), xa1 = gather_x<X32>(x, ca.y), xa2 = gather_x<X32>(x, ca.z), xa3 = gather_x<X32>(x, ca.w);
-        const double xb0 = gather_x<X32>(x, cb.x), xb1 = gather_x<X32>(x, cb.y), xb2 = gather_x<X32>(x, cb.z), xb3 = gather_x<X32>(x, cb.w);
+        const v4i ja = cols.columns(ca), jb = cols.columns(cb);
+        const double xa0 = gather_x<X32>(x, ja.x), xa1 = gather_x<X32>(x, ja.y), xa2 = gather_x<X32>(x, ja.z), xa3 = gather_x<X32>(x, ja.w);
+        const double xb0 = gather_x<X32>(x, jb.x), xb1 = gather_x<X32>(x, jb.y), xb2 = gather_x<X32>(x, jb.z), xb3 = gather_x<X32>(x, jb.w);
         z0 += (double) va.x * xa0;
         z1 += (double) va.y * xa1;
         z2 += (double) va.z * xa2;
@@ -87,26 +96,61 @@ __device__ __forceinline__ double long_row_sum_f32(const int32_t * __restrict__ 
     return group_sum<kWave>((z0 + z1) + (z2 + z3));
 }
 
-template <bool X32>
-__global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const int4 * __restrict__ desc, const int32_t * __restrict__ p,
-                                                               const int32_t * __restrict__ j, const float * __restrict__ a,
-                                                               const double * __restrict__ x, double * y, int exact_order)
+// the caller's 32-bit columns: the stored quad is a 16-byte load and the column is the word
+struct WideColumns {
+    typedef v4i quad;
+    const int32_t * __restrict__ j;
+    __device__ __forceinline__ quad load(int o) const { return *reinterpret_cast<const v4i *>(j + o); }
+    __device__ __forceinline__ v4i columns(quad c) const { return c; }
+    __device__ __forceinline__ int at(int k) const { return j[k]; }
+};
+
+// csr_f32values_kernel's source: j[k] is the column of entry k
+struct WideSource {
+    const int32_t * __restrict__ j;
+    __device__ __forceinline__ int at(int k) const { return j[k]; }
+    // the products of the tile whose first quad starts at entry kb (at = a + kb)
+    template <int QUADS, bool X32>
+    __device__ __forceinline__ void products(double * prod, const float * __restrict__ at, const double * __restrict__ x, int kb,
+                                             int last, int lane) const
+    {
+        quad_products<QUADS, X32>(prod, WideColumns{j + kb}, at, x, last, lane);
+    }
+    template <bool X32>
+    __device__ __forceinline__ double long_row(const float * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
+    {
+        return long_row_sum_f32<X32>(WideColumns{j}, a, x, k0, k1, lane);
+    }
+};
+
+// same-wave LDS operations execute in order; the fences only pin the compiler
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a tile's descriptor and where it ends, wave-uniform
+struct F32Tile {
+    int r0, k0, meta, w, r1, k1;
+};
+__device__ __forceinline__ F32Tile load_f32_tile(const int4 * __restrict__ desc, int w)
+{
+    const TilePair dp = load_tile_pair(desc, w);
+    return F32Tile{__builtin_amdgcn_readfirstlane(dp.d0.x), __builtin_amdgcn_readfirstlane(dp.d0.y), __builtin_amdgcn_readfirstlane(dp.d0.z),
+                   __builtin_amdgcn_readfirstlane(dp.d0.w), __builtin_amdgcn_readfirstlane(dp.d1.x), __builtin_amdgcn_readfirstlane(dp.d1.y)};
+}
+
+// One tile by one wave; prod is the wave's LDS slice (kF32Tile + 4 doubles), src the kernel's column source.
+template <bool X32, class Source>
+__device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const Source src, const int32_t * __restrict__ p,
+                                         const float * __restrict__ a, const double * __restrict__ x, double * y, int exact_order)
 {
     constexpr int TILE = kF32Tile, QUADS = TILE / 256;
-    __shared__ __attribute__((aligned(16))) double prod_all[4][TILE + 4];
-    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
     const int lane = (int) __lane_id();
-    const int w = (int) blockIdx.x * 4 + wave;
-    if (w >= ntiles)
-        return; // whole wave leaves; no workgroup barrier in this kernel
-    double * prod = prod_all[wave];
-    const TilePair dp = load_tile_pair(desc, w);
-    const int r0 = __builtin_amdgcn_readfirstlane(dp.d0.x);
-    const int k0 = __builtin_amdgcn_readfirstlane(dp.d0.y);
-    const int meta = __builtin_amdgcn_readfirstlane(dp.d0.z);
-    const int r1 = __builtin_amdgcn_readfirstlane(dp.d1.x);
-    const int k1 = __builtin_amdgcn_readfirstlane(dp.d1.y);
-    const int nrows = r1 - r0;
+    const int r0 = t.r0, k0 = t.k0, meta = t.meta, k1 = t.k1;
+    const int nrows = t.r1 - r0;
     const int kb = k0 & ~3;
     const int maxlen = meta & 0xFFFF;
     const int lanes_log2 = (meta >> kTileMetaLanesShift) & 0x7;
@@ -127,11 +171,8 @@ __global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const
         }
         const double yv = y[r0 + rowi];
         const int last = (k1 - 1 - kb) & ~3;
-        tile_products_f32<QUADS, X32>(prod, j + kb, a + kb, x, last, lane);
-        // same-wave LDS operations execute in order; the fences only pin the compiler
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        src.template products<QUADS, X32>(prod, a + kb, x, kb, last, lane);
+        wave_lds_fence();
         const int s = ps - kb, e_row = pe - kb;
         double z;
         if (lanes_log2 == 0) { // one lane per row, left to right: the reference's order
@@ -153,10 +194,8 @@ __global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const
         // ---- a tile of empty rows, or the tile whose last quad is not whole (the ragged end of the arrays): entry by entry,
         // one lane per row, left to right
         for (int k = k0 + lane; k < k1; k += kWave)
-            prod[k - kb] = (double) a[k] * x[j[k]];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            prod[k - kb] = (double) a[k] * x[src.at(k)];
+        wave_lds_fence();
         for (int r = lane; r < nrows; r += kWave) {
             const int s = p[r0 + r] - kb, e_row = p[r0 + r + 1] - kb;
             double z = 0.0;
@@ -166,7 +205,7 @@ __global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const
         }
     } else if (!exact_order) {
         // ---- one row longer than a tile: the whole wave, in registers ----
-        const double z = long_row_sum_f32<X32>(j, a, x, k0, k1, lane);
+        const double z = src.template long_row<X32>(a, x, k0, k1, lane);
         if (lane == 0)
             y[r0] = y[r0] + z;
     } else {
@@ -175,20 +214,29 @@ __global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const
         for (int t0 = k0; t0 < k1; t0 += TILE) {
             const int t1 = (t0 + TILE < k1) ? t0 + TILE : k1;
             for (int k = t0 + lane; k < t1; k += kWave)
-                prod[k - t0] = (double) a[k] * x[j[k]];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                prod[k - t0] = (double) a[k] * x[src.at(k)];
+            wave_lds_fence();
             if (lane == 0)
                 for (int k = 0; k < t1 - t0; ++k)
                     z += prod[k];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
         }
         if (lane == 0)
             y[r0] = y[r0] + z;
     }
+}
+
+template <bool X32>
+__global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const int4 * __restrict__ desc, const int32_t * __restrict__ p,
+                                                               const int32_t * __restrict__ j, const float * __restrict__ a,
+                                                               const double * __restrict__ x, double * y, int exact_order)
+{
+    __shared__ __attribute__((aligned(16))) double prod_all[4][kF32Tile + 4];
+    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
+    const int w = (int) blockIdx.x * 4 + wave;
+    if (w >= ntiles)
+        return; // whole wave leaves; no workgroup barrier in this kernel
+    f32_tile<X32>(prod_all[wave], load_f32_tile(desc, w), WideSource{j}, p, a, x, y, exact_order);
 }
 
 // spmv_hip_narrow_values: out[k] = (float) value[k]; per workgroup {values that changed, finite values that became infinite,

@@ -1,7 +1,7 @@
 // f32values.hip -- include/spmv_hip_f32values.h: y += fl32(A) x with the values stored and streamed as 4-byte floats.  The plan
 // cuts the rows into wave tiles on the host from row_ptr alone (the plain tiles of plan_csr.hip: lanes per row from the tile's
 // longest row, at most 16 entries per lane); the kernel is csr_f32values.hpp.
-#include "internal.hpp"
+#include "f32_plan.hpp"
 #include "csr_f32values.hpp"
 
 #include <algorithm>
@@ -11,36 +11,7 @@
 
 using namespace spmvi;
 
-struct spmv_hip_f32_plan {
-    int32_t rows = 0, cols = 0, nnz = 0;
-    unsigned flags = 0;
-    int ntiles = 0, long_tiles = 0, uniform_tiles = 0, scalar_tiles = 0, longest = 0;
-    long long streamed_bytes = 0;
-    size_t device_bytes = 0;
-    int4 * d_desc = nullptr; // ntiles + 1 records
-};
-
 namespace {
-
-int check_host(int32_t rows, int32_t cols, const int32_t * rp, unsigned flags)
-{
-    if (rows < 0 || cols < 0 || !rp)
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
-    if (flags & ~SPMV_HIP_FLAG_EXACT_ORDER)
-        return fail(SPMV_HIP_ERR_INVALID, "unknown flag bits (0 or SPMV_HIP_FLAG_EXACT_ORDER)");
-    if (rp[0] != 0)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[0] must be 0");
-    for (int32_t r = 0; r < rows; ++r)
-        if (rp[r + 1] < rp[r])
-            return fail(SPMV_HIP_ERR_INVALID, "row_ptr must be non-decreasing");
-    return SPMV_HIP_OK;
-}
-
-// what the preview and the plan share: every number of plan_info and the descriptors
-struct HostPlan {
-    spmv_hip_f32_plan numbers;
-    std::vector<int4> desc;
-};
 
 int lanes_for(int len)
 {
@@ -50,7 +21,66 @@ int lanes_for(int len)
     return l;
 }
 
-void plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, unsigned flags)
+void plan_numbers(const spmv_hip_f32_plan & pl, int64_t * out, int n)
+{
+    const int64_t v[SPMV_HIP_F32_INFO] = {pl.rows, pl.cols, pl.nnz, pl.ntiles, pl.long_tiles, pl.longest, pl.flags,
+                                          (int64_t) pl.device_bytes, pl.streamed_bytes, pl.uniform_tiles, pl.scalar_tiles,
+                                          (pl.ntiles + 3) / 4};
+    for (int i = 0; i < n && i < SPMV_HIP_F32_INFO; ++i)
+        out[i] = v[i];
+}
+
+// the host plan onto the current device
+int build_plan(spmv_hip_f32_plan ** out, F32HostPlan const & hp, hipStream_t s)
+{
+    spmv_hip_f32_plan * pl = new (std::nothrow) spmv_hip_f32_plan(hp.numbers);
+    if (!pl)
+        return fail(SPMV_HIP_ERR_ALLOC, "plan allocation failed");
+    if (!hp.desc.empty()) {
+        hipError_t e = hipMalloc((void **) &pl->d_desc, hp.desc.size() * sizeof(int4));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(pl->d_desc, hp.desc.data(), hp.desc.size() * sizeof(int4), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            spmv_hip_f32_plan_destroy(pl);
+            return fail_hip(e, "fp32-value plan: tile descriptors");
+        }
+    }
+    *out = pl;
+    return SPMV_HIP_OK;
+}
+
+int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_err)
+{
+    if (c.overflow > 0) {
+        char text[160];
+        std::snprintf(text, sizeof text, "%lld finite value(s) are infinite as floats (the first is entry %lld)", c.overflow, c.first_overflow);
+        return fail(SPMV_HIP_ERR_OVERFLOW, text);
+    }
+    if (inexact)
+        *inexact = c.inexact;
+    if (max_rel_err)
+        *max_rel_err = c.max_rel;
+    return SPMV_HIP_OK;
+}
+
+} // namespace
+
+// ---- what compact.hip shares (f32_plan.hpp) ------------------------------------------------------------------------------------
+
+namespace spmvi {
+
+int f32_check_host(int32_t rows, int32_t cols, const int32_t * rp, unsigned flags)
+{
+    if (rows < 0 || cols < 0 || !rp)
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
+    if (flags & ~SPMV_HIP_FLAG_EXACT_ORDER)
+        return fail(SPMV_HIP_ERR_INVALID, "unknown flag bits (0 or SPMV_HIP_FLAG_EXACT_ORDER)");
+    return check_row_ptr_order(rows, rp);
+}
+
+void f32_plan_host(F32HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, unsigned flags)
 {
     spmv_hip_f32_plan & pl = hp.numbers;
     const int32_t nnz = p[rows];
@@ -107,41 +137,6 @@ void plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, uns
     pl.streamed_bytes = 8LL * nnz + row_ptr_bytes + 16LL * rows + 8LL * cols + 16LL * (pl.ntiles + 1);
 }
 
-void plan_numbers(const spmv_hip_f32_plan & pl, int64_t * out, int n)
-{
-    const int64_t v[SPMV_HIP_F32_INFO] = {pl.rows, pl.cols, pl.nnz, pl.ntiles, pl.long_tiles, pl.longest, pl.flags,
-                                          (int64_t) pl.device_bytes, pl.streamed_bytes, pl.uniform_tiles, pl.scalar_tiles,
-                                          (pl.ntiles + 3) / 4};
-    for (int i = 0; i < n && i < SPMV_HIP_F32_INFO; ++i)
-        out[i] = v[i];
-}
-
-// the host plan onto the current device
-int build_plan(spmv_hip_f32_plan ** out, HostPlan const & hp, hipStream_t s)
-{
-    spmv_hip_f32_plan * pl = new (std::nothrow) spmv_hip_f32_plan(hp.numbers);
-    if (!pl)
-        return fail(SPMV_HIP_ERR_ALLOC, "plan allocation failed");
-    if (!hp.desc.empty()) {
-        hipError_t e = hipMalloc((void **) &pl->d_desc, hp.desc.size() * sizeof(int4));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(pl->d_desc, hp.desc.data(), hp.desc.size() * sizeof(int4), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            spmv_hip_f32_plan_destroy(pl);
-            return fail_hip(e, "fp32-value plan: tile descriptors");
-        }
-    }
-    *out = pl;
-    return SPMV_HIP_OK;
-}
-
-struct NarrowResult {
-    long long inexact = 0, overflow = 0, first_inexact = -1, first_overflow = -1;
-    double max_rel = 0.0;
-};
-
 NarrowResult narrow_host(int64_t n, const double * value, float * out)
 {
     NarrowResult c;
@@ -166,21 +161,18 @@ NarrowResult narrow_host(int64_t n, const double * value, float * out)
     return c;
 }
 
-int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_err)
+int narrow_refusal(NarrowResult const & c, int allow_rounding)
 {
-    if (c.overflow > 0) {
-        char text[160];
-        std::snprintf(text, sizeof text, "%lld finite value(s) are infinite as floats (the first is entry %lld)", c.overflow, c.first_overflow);
-        return fail(SPMV_HIP_ERR_OVERFLOW, text);
-    }
-    if (inexact)
-        *inexact = c.inexact;
-    if (max_rel_err)
-        *max_rel_err = c.max_rel;
-    return SPMV_HIP_OK;
+    const int rc = narrow_report(c, nullptr, nullptr);
+    if (rc != 0 || c.inexact == 0 || allow_rounding)
+        return rc;
+    char text[200];
+    std::snprintf(text, sizeof text, "%lld value(s) are not floats (the first is entry %lld, relative change at most %.3g) and allow_rounding is 0",
+                  c.inexact, c.first_inexact, c.max_rel);
+    return fail(SPMV_HIP_ERR_INVALID, text);
 }
 
-} // namespace
+} // namespace spmvi
 
 extern "C" {
 
@@ -229,11 +221,11 @@ int spmv_hip_f32_plan_preview(int32_t rows, int32_t cols, const int32_t * host_r
     if (!out || n < 0 || tile_table_ints < 0)
         return fail(SPMV_HIP_ERR_INVALID, "out is null, or a negative count");
     int rc;
-    if ((rc = check_host(rows, cols, host_row_ptr, flags)) != 0)
+    if ((rc = f32_check_host(rows, cols, host_row_ptr, flags)) != 0)
         return rc;
-    HostPlan hp;
+    F32HostPlan hp;
     try {
-        plan_host(hp, rows, cols, host_row_ptr, flags);
+        f32_plan_host(hp, rows, cols, host_row_ptr, flags);
     } catch (std::bad_alloc const &) {
         return fail(SPMV_HIP_ERR_ALLOC, "fp32-value plan: host memory");
     }
@@ -259,11 +251,11 @@ int spmv_hip_f32_plan_csr(spmv_hip_f32_plan ** plan, int32_t rows, int32_t cols,
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
     *plan = nullptr;
     int rc;
-    if ((rc = check_host(rows, cols, host_row_ptr, flags)) != 0)
+    if ((rc = f32_check_host(rows, cols, host_row_ptr, flags)) != 0)
         return rc;
-    HostPlan hp;
+    F32HostPlan hp;
     try {
-        plan_host(hp, rows, cols, host_row_ptr, flags);
+        f32_plan_host(hp, rows, cols, host_row_ptr, flags);
     } catch (std::bad_alloc const &) {
         return fail(SPMV_HIP_ERR_ALLOC, "fp32-value plan: host memory");
     }
@@ -326,7 +318,7 @@ int spmv_hip_upload_csr_f32values(spmv_hip_ctx * c, int32_t rows, int32_t cols, 
     if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
         return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
     const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
-    int rc = check_host(rows, cols, row_ptr, flags);
+    int rc = f32_check_host(rows, cols, row_ptr, flags);
     if (rc != 0)
         return rc;
     if (row_ptr[rows] != nnz)
@@ -338,19 +330,12 @@ int spmv_hip_upload_csr_f32values(spmv_hip_ctx * c, int32_t rows, int32_t cols, 
         return fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)");
     // everything that can refuse the matrix happens before anything is freed or copied
     std::vector<float> narrow;
-    HostPlan hp;
+    F32HostPlan hp;
     try {
         narrow.resize((size_t) nnz);
-        const NarrowResult nr = narrow_host(nnz, value, narrow.data());
-        if ((rc = narrow_report(nr, nullptr, nullptr)) != 0)
+        if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
             return rc;
-        if (nr.inexact > 0 && !allow_rounding) {
-            char text[200];
-            std::snprintf(text, sizeof text, "%lld value(s) are not floats (the first is entry %lld, relative change at most %.3g) and allow_rounding is 0",
-                          nr.inexact, nr.first_inexact, nr.max_rel);
-            return fail(SPMV_HIP_ERR_INVALID, text);
-        }
-        plan_host(hp, rows, cols, row_ptr, flags);
+        f32_plan_host(hp, rows, cols, row_ptr, flags);
     } catch (std::bad_alloc const &) {
         return fail(SPMV_HIP_ERR_ALLOC, "fp32-value upload: host memory");
     }
@@ -359,41 +344,11 @@ int spmv_hip_upload_csr_f32values(spmv_hip_ctx * c, int32_t rows, int32_t cols, 
     free_ctx_matrix(c);
     if ((rc = build_plan(&c->f32_plan, hp, c->stream)) != 0)
         return rc;
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr, column_index, true, narrow.data(), true)) != 0)
+        return rc;
     c->rows = rows;
     c->cols = cols;
     c->nnz = nnz;
-    auto alloc = [&](void ** p, size_t bytes) -> int {
-        hipError_t e = hipMalloc(p, bytes + 64);
-        if (e != hipSuccess)
-            return fail_hip(e, "hipMalloc");
-        c->bytes += bytes + 64;
-        return SPMV_HIP_OK;
-    };
-    auto cleanup = [&](int code) {
-        std::string const why = last_error_text();
-        free_ctx_matrix(c);
-        set_last_error_text(why);
-        return code;
-    };
-    if ((rc = alloc((void **) &c->d_ptr, ((size_t) rows + 1) * sizeof(int32_t))) != 0 ||
-        (rc = alloc((void **) &c->d_col, (size_t) nnz * sizeof(int32_t))) != 0 ||
-        (rc = alloc((void **) &c->d_val32, (size_t) nnz * sizeof(float))) != 0 ||
-        (rc = alloc((void **) &c->d_x, (size_t) cols * sizeof(double))) != 0 ||
-        (rc = alloc((void **) &c->d_y, (size_t) rows * sizeof(double))) != 0)
-        return cleanup(rc);
-    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, ((size_t) rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_col, column_index, (size_t) nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_val32, narrow.data(), (size_t) nnz * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_x, 0, (size_t) cols * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_y, 0, (size_t) rows * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-        return cleanup(fail_hip(e, "upload (host arrays -> device)"));
     c->bytes += c->f32_plan->device_bytes;
     c->format = 7;
     return SPMV_HIP_OK;

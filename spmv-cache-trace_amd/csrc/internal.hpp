@@ -12,6 +12,8 @@
 //   transpose.hip    y += A' x from the CSR arrays of A as they are (spmv_hip_transpose.h)
 //   f32values.hip    y += fl32(A) x with the values stored as 4-byte floats (spmv_hip_f32values.h)
 //   compact.hip      ... and the columns of a tile as 16-bit window codes (spmv_hip_compact.h)
+// The last two share one tiling rule and the narrowing of the values (f32_plan.hpp, defined in f32values.hip) and one tile
+// kernel body over three column sources (csr_f32values.hpp: f32_tile; csr_compact.hpp adds the two code sources).
 #pragma once
 
 #include "spmv_hip_plan.h"
@@ -37,6 +39,10 @@ namespace spmvi {
 // last error text of the calling thread (spmv_hip_last_error); fail() returns `code` after recording `what`
 int fail(int code, const char * what);
 int fail_hip(hipError_t e, const char * call);
+// rows < 0, cols < 0 or row_ptr null; row_ptr[0] != 0; row_ptr decreasing -- refused in that order (SPMV_HIP_ERR_INVALID)
+int check_csr_row_ptr(int32_t rows, int32_t cols, const int32_t * row_ptr);
+// ... the last two alone, for a caller whose first message differs (rows >= 0, row_ptr not null)
+int check_row_ptr_order(int32_t rows, const int32_t * row_ptr);
 std::string last_error_text();
 void set_last_error_text(std::string const & text);
 
@@ -286,6 +292,11 @@ void drop_stencil_runs(spmv_hip_plan * pl);
 
 // context.hip
 void free_ctx_matrix(spmv_hip_ctx * c);
+// The device side of a Level-1 CSR upload into a context whose matrix was freed: row_ptr (nptr entries), the columns (unless
+// !keep_columns: no d_col), the nnz values (doubles into d_val or, with float_values, floats into d_val32) and zeroed x (nx) and y (ny), every array
+// padded by 64 bytes and counted in c->bytes; synchronises.  On failure the matrix is freed and the first error text kept.
+int upload_ctx_csr(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr, const int32_t * column_index,
+                   bool keep_columns, const void * value, bool float_values);
 
 // multi_gpu.hip
 void multi_free_matrix(spmv_hip_ctx * c);

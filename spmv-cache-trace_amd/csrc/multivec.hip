@@ -29,11 +29,8 @@ int check_row_ptr(int32_t rows, int32_t cols, const int32_t * rp)
 {
     if (rows < 0 || cols < 0 || !rp)
         return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows or cols < 0, or row_ptr null)");
-    if (rp[0] != 0)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[0] must be 0");
-    for (int32_t r = 0; r < rows; ++r)
-        if (rp[r + 1] < rp[r])
-            return fail(SPMV_HIP_ERR_INVALID, "row_ptr must be non-decreasing");
+    if (int rc = check_row_ptr_order(rows, rp))
+        return rc;
     if (rp[rows] > 0 && cols == 0)
         return fail(SPMV_HIP_ERR_INVALID, "entries in a matrix without columns");
     return SPMV_HIP_OK;

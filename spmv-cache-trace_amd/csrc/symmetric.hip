@@ -39,12 +39,7 @@ int check_csr_host(int32_t rows, const int32_t * rp)
 {
     if (rows < 0 || !rp)
         return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0 or row_ptr null)");
-    if (rp[0] != 0)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[0] must be 0");
-    for (int32_t r = 0; r < rows; ++r)
-        if (rp[r + 1] < rp[r])
-            return fail(SPMV_HIP_ERR_INVALID, "row_ptr must be non-decreasing");
-    return SPMV_HIP_OK;
+    return check_row_ptr_order(rows, rp);
 }
 
 // triangle + diagonal count + column range check; row_ptr already checked
@@ -402,41 +397,11 @@ int spmv_hip_upload_csr_symmetric(spmv_hip_ctx * c, int32_t rows, int32_t nnz, c
     // the plan first: it refuses what is not a stored triangle before anything is copied
     if ((rc = build_sym_plan(&c->sym_plan, rows, row_ptr, column_index, kind, 0, 0)) != 0)
         return rc;
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) rows, (size_t) rows, (size_t) nnz, row_ptr, column_index, true, value, false)) != 0)
+        return rc;
     c->rows = rows;
     c->cols = rows;
     c->nnz = nnz;
-    auto alloc = [&](void ** p, size_t bytes) -> int {
-        hipError_t e = hipMalloc(p, bytes + 64);
-        if (e != hipSuccess)
-            return fail_hip(e, "hipMalloc");
-        c->bytes += bytes + 64;
-        return SPMV_HIP_OK;
-    };
-    auto cleanup = [&](int code) {
-        std::string const why = last_error_text();
-        free_ctx_matrix(c);
-        set_last_error_text(why);
-        return code;
-    };
-    if ((rc = alloc((void **) &c->d_ptr, ((size_t) rows + 1) * sizeof(int32_t))) != 0 ||
-        (rc = alloc((void **) &c->d_col, (size_t) nnz * sizeof(int32_t))) != 0 ||
-        (rc = alloc((void **) &c->d_val, (size_t) nnz * sizeof(double))) != 0 ||
-        (rc = alloc((void **) &c->d_x, (size_t) rows * sizeof(double))) != 0 ||
-        (rc = alloc((void **) &c->d_y, (size_t) rows * sizeof(double))) != 0)
-        return cleanup(rc);
-    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, ((size_t) rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_col, column_index, (size_t) nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_val, value, (size_t) nnz * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_x, 0, (size_t) rows * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_y, 0, (size_t) rows * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-        return cleanup(fail_hip(e, "upload (host arrays -> device)"));
     c->bytes += c->sym_plan->device_bytes;
     c->format = 5;
     return SPMV_HIP_OK;

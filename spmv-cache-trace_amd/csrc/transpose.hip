@@ -30,18 +30,6 @@ constexpr int kTrAutoWindows = 4;          // the spilled share of 
 constexpr size_t kTrLdsBytes = 80 * 1024;  // per workgroup: two workgroups of 512 threads per CU (160 KB)
 constexpr int kTrBucket = 32;              // window boundaries in steps of 32 doubles (256 B)
 
-int check_tr_host(int32_t rows, int32_t cols, const int32_t * rp)
-{
-    if (rows < 0 || cols < 0 || !rp)
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0, cols < 0 or row_ptr null)");
-    if (rp[0] != 0)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[0] must be 0");
-    for (int32_t r = 0; r < rows; ++r)
-        if (rp[r + 1] < rp[r])
-            return fail(SPMV_HIP_ERR_INVALID, "row_ptr must be non-decreasing");
-    return SPMV_HIP_OK;
-}
-
 int check_windows_args(int max_windows, int window_doubles)
 {
     if (max_windows < 0 || max_windows > spmv::kTrMaxWindows || window_doubles < 0)
@@ -285,7 +273,7 @@ int spmv_hip_tr_plan_preview(int32_t rows, int32_t cols, const int32_t * host_ro
     if (!out || n < 0 || window_table_ints < 0)
         return fail(SPMV_HIP_ERR_INVALID, "out is null, or a negative count");
     int rc;
-    if ((rc = check_tr_host(rows, cols, host_row_ptr)) != 0 || (rc = check_windows_args(max_windows, window_doubles)) != 0)
+    if ((rc = check_csr_row_ptr(rows, cols, host_row_ptr)) != 0 || (rc = check_windows_args(max_windows, window_doubles)) != 0)
         return rc;
     HostPlan hp;
     try {
@@ -313,7 +301,7 @@ int spmv_hip_tr_plan_csr(spmv_hip_tr_plan ** plan, int32_t rows, int32_t cols, c
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
     *plan = nullptr;
     int rc;
-    if ((rc = check_tr_host(rows, cols, host_row_ptr)) != 0 || (rc = check_windows_args(max_windows, window_doubles)) != 0)
+    if ((rc = check_csr_row_ptr(rows, cols, host_row_ptr)) != 0 || (rc = check_windows_args(max_windows, window_doubles)) != 0)
         return rc;
     const int32_t nnz = host_row_ptr[rows];
     if (nnz > 0 && !d_column_index)
@@ -395,7 +383,7 @@ int spmv_hip_upload_csr_transposed(spmv_hip_ctx * c, int32_t rows, int32_t cols,
         return fail(SPMV_HIP_ERR_INVALID, "SPMV_HIP_FLAG_EXACT_ORDER cannot be kept: a transposed multiply adds its products with atomics");
     if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
         return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
-    int rc = check_tr_host(rows, cols, row_ptr);
+    int rc = check_csr_row_ptr(rows, cols, row_ptr);
     if (rc != 0)
         return rc;
     if (row_ptr[rows] != nnz)
@@ -414,41 +402,11 @@ int spmv_hip_upload_csr_transposed(spmv_hip_ctx * c, int32_t rows, int32_t cols,
     if ((rc = build_tr_plan(&c->tr_plan, hp)) != 0)
         return rc;
     // the context holds the operator that runs, A': its x has `rows` entries and its y `cols`
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) rows, (size_t) cols, (size_t) nnz, row_ptr, column_index, true, value, false)) != 0)
+        return rc;
     c->rows = cols;
     c->cols = rows;
     c->nnz = nnz;
-    auto alloc = [&](void ** p, size_t bytes) -> int {
-        hipError_t e = hipMalloc(p, bytes + 64);
-        if (e != hipSuccess)
-            return fail_hip(e, "hipMalloc");
-        c->bytes += bytes + 64;
-        return SPMV_HIP_OK;
-    };
-    auto cleanup = [&](int code) {
-        std::string const why = last_error_text();
-        free_ctx_matrix(c);
-        set_last_error_text(why);
-        return code;
-    };
-    if ((rc = alloc((void **) &c->d_ptr, ((size_t) rows + 1) * sizeof(int32_t))) != 0 ||
-        (rc = alloc((void **) &c->d_col, (size_t) nnz * sizeof(int32_t))) != 0 ||
-        (rc = alloc((void **) &c->d_val, (size_t) nnz * sizeof(double))) != 0 ||
-        (rc = alloc((void **) &c->d_x, (size_t) rows * sizeof(double))) != 0 ||
-        (rc = alloc((void **) &c->d_y, (size_t) cols * sizeof(double))) != 0)
-        return cleanup(rc);
-    hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, ((size_t) rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_col, column_index, (size_t) nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(c->d_val, value, (size_t) nnz * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_x, 0, (size_t) rows * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_y, 0, (size_t) cols * sizeof(double), c->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-        return cleanup(fail_hip(e, "upload (host arrays -> device)"));
     c->bytes += c->tr_plan->device_bytes;
     c->format = 6;
     return SPMV_HIP_OK;
