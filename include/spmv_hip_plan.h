@@ -143,7 +143,9 @@ void spmv_hip_plan_destroy(spmv_hip_plan *plan);
  *        [37] the rows per group of those tiles (0 = none)
  *        [38] chunks of stencil row runs (up to 128 rows each; 0 = none, see SPMV_HIP_FLAG_NO_STENCIL_RUNS)  [39] tiles merged
  *             into those runs  [40] their entries  [41] chunks among [38] that hold a row with missing positions (row masks)
- *        [42] tiles left to a second launch beside the runs (0 with runs: one launch) */
+ *        [42] tiles left to a second launch beside the runs (0 with runs: one launch)
+ *        [43] the run kernel: 0 no runs, 1 the row-chunk kernel (2 is kept for a variant of it), + 4 where the plan's odd launches
+ *             sweep the chunks backwards (same y; a multiply then starts on the rows the one before left in the Infinity Cache) */
 int spmv_hip_plan_info(const spmv_hip_plan *plan, int64_t *out, int n);
 
 /* y += A*x, CSR.  Replaces csr_spmv / csr_spmv_inner_loop

@@ -30,6 +30,11 @@
 // Infinity Cache; 169 -> 156 us on Poisson 4096^2).  DENSE (chunk c is rows [128 c, 128 c + 128) for every c, and the plan asked
 // for it): the rows follow from the chunk's number, not from the descriptor -- measured no faster, so plans leave it off.
 //
+// Sweep (round 10): x and y (the next step's y_in) are what a step leaves in the 256 MiB Infinity Cache.  A plan's odd launches
+// take the chunks backwards (RunPattern::mirror: whole groups of 8 workgroups mirrored, so a chunk stays on its XCD), and a step
+// starts on the rows the step before touched last; with every sweep forward an LRU-like cache that is a little too small holds
+// nothing of them by the time they are needed.  YIN_NT / YOUT_NT: `nt` on the y_in load and the y store, the plan's choice.
+//
 // A grid of resident waves that each walk many chunks was slower (212 against 180 us on Poisson 4096^2): the dispatcher's refill of
 // finished waves hides a chunk's vmcnt(0) better than a fixed set of waves.
 #pragma once
@@ -46,8 +51,11 @@ constexpr int kRunLen = 5;   // positions of the run pattern
 constexpr int kRunSlot = kRunLen * 128;
 
 // the run pattern by value: row + rel[p] is position p's column, rel ascending
+// `mirror`: 0, or the number G of groups of 8 workgroups in the grid -- workgroup b then takes the chunks of workgroup
+// ((G - 1 - (b >> 3)) << 3) | (b & 7): the sweep backwards, every chunk on the XCD (b mod 8) it has in the forward sweep
 struct RunPattern {
     int rel[kRunLen];
+    int mirror;
 };
 
 // A chunk: {first row, first entry, rows (2 ... 128) | entries << 8, mask slot or -1}; its entries are [first entry, + entries),
@@ -85,35 +93,51 @@ __device__ __forceinline__ void run_values_lds(const unsigned (&lds)[kRunLen], c
 // y_in, the five x pairs and one more load (`global_load_dwordx2` of a full chunk's last entry, or `global_load_ushort` of a masked
 // chunk's two row masks) behind the value loads, then the chunk's one wait: loads and wait in one statement, so hipcc neither waits
 // between them nor touches the destinations before the data is there.
-#define SPMV_RUN_ISSUE(LAST)                                                                                                   \
+#define SPMV_RUN_ISSUE(YNT, LAST)                                                                                                \
     "s_nop 4\n\t"                                                                                                              \
-    "global_load_dwordx4 %0, %7, %8 nt\n\t"                                                                                    \
+    "global_load_dwordx4 %0, %7, %8" YNT "\n\t"                                                                                 \
     "global_load_dwordx4 %1, %9, %14\n\t"                                                                                      \
     "global_load_dwordx4 %2, %10, %14\n\t"                                                                                     \
     "global_load_dwordx4 %3, %11, %14\n\t"                                                                                     \
     "global_load_dwordx4 %4, %12, %14\n\t"                                                                                     \
     "global_load_dwordx4 %5, %13, %14\n\t" LAST " %6, %15, %16\n\t"                                                            \
     "s_waitcnt vmcnt(0)"
+#define SPMV_RUN_ISSUE_FULL(YNT)                                                                                               \
+    asm volatile(SPMV_RUN_ISSUE(YNT, "global_load_dwordx2")                                                                    \
+                 : "=&v"(yv), "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]), "=&v"(xv[4]), "=&v"(last)                \
+                 : "v"(yo), "s"(yb), "v"(xo[0]), "v"(xo[1]), "v"(xo[2]), "v"(xo[3]), "v"(xo[4]), "s"(x), "v"(lo), "s"(ak)      \
+                 : "memory")
+#define SPMV_RUN_ISSUE_MASKED(YNT)                                                                                             \
+    asm volatile(SPMV_RUN_ISSUE(YNT, "global_load_ushort")                                                                     \
+                 : "=&v"(yv), "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]), "=&v"(xv[4]), "=&v"(m2)                  \
+                 : "v"(yo), "s"(yb), "v"(xo[0]), "v"(xo[1]), "v"(xo[2]), "v"(xo[3]), "v"(xo[4]), "s"(x), "v"(mo), "s"(mk)      \
+                 : "memory")
+// YIN_NT: the y_in load carries `nt` (x never does: it is the stream that is to stay in the Infinity Cache)
+template <bool YIN_NT>
 __device__ __forceinline__ void run_issue_full(v2d_a8 & yv, v2d_a8 (&xv)[kRunLen], double & last, unsigned yo, const double * yb,
                                                const unsigned (&xo)[kRunLen], const double * x, unsigned lo, const double * ak)
 {
-    asm volatile(SPMV_RUN_ISSUE("global_load_dwordx2")
-                 : "=&v"(yv), "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]), "=&v"(xv[4]), "=&v"(last)
-                 : "v"(yo), "s"(yb), "v"(xo[0]), "v"(xo[1]), "v"(xo[2]), "v"(xo[3]), "v"(xo[4]), "s"(x), "v"(lo), "s"(ak)
-                 : "memory");
+    if (YIN_NT)
+        SPMV_RUN_ISSUE_FULL(" nt");
+    else
+        SPMV_RUN_ISSUE_FULL("");
 }
+template <bool YIN_NT>
 __device__ __forceinline__ void run_issue_masked(v2d_a8 & yv, v2d_a8 (&xv)[kRunLen], unsigned & m2, unsigned yo, const double * yb,
                                                  const unsigned (&xo)[kRunLen], const double * x, unsigned mo, const uint8_t * mk)
 {
-    asm volatile(SPMV_RUN_ISSUE("global_load_ushort")
-                 : "=&v"(yv), "=&v"(xv[0]), "=&v"(xv[1]), "=&v"(xv[2]), "=&v"(xv[3]), "=&v"(xv[4]), "=&v"(m2)
-                 : "v"(yo), "s"(yb), "v"(xo[0]), "v"(xo[1]), "v"(xo[2]), "v"(xo[3]), "v"(xo[4]), "s"(x), "v"(mo), "s"(mk)
-                 : "memory");
+    if (YIN_NT)
+        SPMV_RUN_ISSUE_MASKED(" nt");
+    else
+        SPMV_RUN_ISSUE_MASKED("");
 }
+#undef SPMV_RUN_ISSUE_MASKED
+#undef SPMV_RUN_ISSUE_FULL
 #undef SPMV_RUN_ISSUE
 
 // A wave per chunk.  hipcc counts none of the chunk's loads (inline asm): run_issue_* waits for all of them at once.
-template <bool DENSE, bool NT>
+// YIN_NT, YOUT_NT: the y_in load and the y store carry `nt` (round 10's A/B).
+template <bool DENSE, bool NT, bool YIN_NT = true, bool YOUT_NT = true>
 __global__ __launch_bounds__(256) void csr_runs_kernel(int nchunks, int rows, int cols, const int4 * __restrict__ chunks,
                                                        const uint8_t * __restrict__ masks, RunPattern pat, const double * __restrict__ a,
                                                        const double * __restrict__ x, const double * y_in, double * y)
@@ -121,10 +145,12 @@ __global__ __launch_bounds__(256) void csr_runs_kernel(int nchunks, int rows, in
     __shared__ __attribute__((aligned(16))) double slots[kRunWaves][kRunSlot];
     const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
     const int lane = (int) __lane_id();
-    const int c = (int) blockIdx.x * kRunWaves + wave;
+    // (the asm below holds the arguments; the mirrored workgroup number costs three scalar instructions)
     // every kernel argument in one scalar round trip (else hipcc loads them next to their first uses, one wait each)
     asm volatile("" ::"s"(nchunks), "s"(rows), "s"(cols), "s"(chunks), "s"(masks), "s"(pat.rel[0]), "s"(pat.rel[1]), "s"(pat.rel[2]),
-                 "s"(pat.rel[3]), "s"(pat.rel[4]), "s"(a), "s"(x), "s"(y_in), "s"(y));
+                 "s"(pat.rel[3]), "s"(pat.rel[4]), "s"(pat.mirror), "s"(a), "s"(x), "s"(y_in), "s"(y));
+    const int b = (int) blockIdx.x;
+    const int c = (pat.mirror ? ((pat.mirror - 1 - (b >> 3)) << 3) | (b & 7) : b) * kRunWaves + wave;
     if (c >= nchunks)
         return;
     const double * slot = slots[wave];
@@ -159,7 +185,7 @@ __global__ __launch_bounds__(256) void csr_runs_kernel(int nchunks, int rows, in
     if (mslot < 0) { // every row holds all five positions
         double last;
         // (a full chunk's rows hold all five columns: every pair lies inside [0, cols), as loaded)
-        run_issue_full(yv, xl, last, 8u * (unsigned) base, y_in + row0, xo, x, 8u * (unsigned) (lead + entries - 1), ak);
+        run_issue_full<YIN_NT>(yv, xl, last, 8u * (unsigned) base, y_in + row0, xo, x, 8u * (unsigned) (lead + entries - 1), ak);
         const double * v = slot + lead + base * kRunLen;
         // the chunk's last entry is the last row's position 4 (slot index lead + 5 n - 1, past the slot when n = 128, lead = 1)
         const double vlast = base == n - 2 ? last : slot[min(lead + base * kRunLen + 2 * kRunLen - 1, kRunSlot - 1)];
@@ -171,7 +197,7 @@ __global__ __launch_bounds__(256) void csr_runs_kernel(int nchunks, int rows, in
     } else {
         // rows 2l, 2l + 1 of the lane: one 2-byte load (a slot's masks past the chunk's rows are 0)
         unsigned m2;
-        run_issue_masked(yv, xl, m2, 8u * (unsigned) base, y_in + row0, xo, x, 2u * (unsigned) lane, masks + (size_t) mslot * kRunChunkRows);
+        run_issue_masked<YIN_NT>(yv, xl, m2, 8u * (unsigned) base, y_in + row0, xo, x, 2u * (unsigned) lane, masks + (size_t) mslot * kRunChunkRows);
         v2d_a8 xv[kRunLen];
 #pragma unroll
         for (int p = 0; p < kRunLen; ++p) // a missing column is never used
@@ -205,9 +231,15 @@ __global__ __launch_bounds__(256) void csr_runs_kernel(int nchunks, int rows, in
     }
     if (2 * lane <= n - 2) {
         const v2d_a8 out = {yv.x + zA, yv.y + zB};
-        __builtin_nontemporal_store(out, reinterpret_cast<v2d_a8 *>(y + row0 + base));
+        if (YOUT_NT)
+            __builtin_nontemporal_store(out, reinterpret_cast<v2d_a8 *>(y + row0 + base));
+        else
+            *reinterpret_cast<v2d_a8 *>(y + row0 + base) = out;
     } else if (2 * lane == n - 1) {
-        __builtin_nontemporal_store(yv.y + zB, y + row0 + base + 1);
+        if (YOUT_NT)
+            __builtin_nontemporal_store(yv.y + zB, y + row0 + base + 1);
+        else
+            y[row0 + base + 1] = yv.y + zB;
     }
 }
 

@@ -137,6 +137,11 @@ struct spmv_hip_plan {
     spmv::RunPattern run_pattern{};
     bool run_dense = false; // chunk c is rows [128 c, 128 c + 128): the kernel takes the rows from the chunk number
     bool run_nt = false;    // the value loads carry `nt`
+    // round 10: the y_in load and the y store carry `nt`; odd launches of the run kernel sweep the chunks backwards,
+    // so that a multiply starts on the rows of x and y the one before touched last (what the Infinity Cache still holds).  Both
+    // directions give the same y, so the counter is relaxed: launches that race on it only lose cache hits.
+    bool run_yin_nt = true, run_yout_nt = true, run_sweep = false;
+    mutable std::atomic<unsigned> run_launches{0};
     // row-group plans (csr_rowgroup.hpp): the tiles csr_rowgroup_kernel multiplies, and the others (csr_wavetile_kernel<LIST>)
     int32_t * d_group_tiles = nullptr, * d_group_rest = nullptr;
     int ngroup_tiles = 0, ngroup_rest = 0;

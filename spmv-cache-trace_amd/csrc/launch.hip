@@ -12,6 +12,14 @@ using namespace spmvi;
 
 namespace {
 
+// csr_runs_kernel by its cache policies (the plan's switches)
+template <bool DENSE, bool NT>
+static auto run_kernel(bool yin_nt, bool yout_nt) -> decltype(&spmv::csr_runs_kernel<DENSE, NT, true, true>)
+{
+    return yin_nt ? (yout_nt ? spmv::csr_runs_kernel<DENSE, NT, true, true> : spmv::csr_runs_kernel<DENSE, NT, true, false>)
+                  : (yout_nt ? spmv::csr_runs_kernel<DENSE, NT, false, true> : spmv::csr_runs_kernel<DENSE, NT, false, false>);
+}
+
 template <int LPR>
 void launch_vector(const spmv_hip_plan * pl, const int32_t * p, const int32_t * j, const double * a,
                    const double * x, double * y, hipStream_t s)
@@ -250,11 +258,21 @@ static int csr_spmv_launch(const spmv_hip_plan * pl, const int32_t * p, const in
             ) {
                 // stencil row runs (csr_runs.hpp): a wave per chunk of 128 rows (a grid of resident waves that walk the chunks measured
                 // 212 against 188 us on Poisson 4096^2; a wave per chunk 180), then the other tiles, if any
-                const dim3 grid((unsigned) ((pl->nrun_chunks + spmv::kRunWaves - 1) / spmv::kRunWaves));
-                auto runs = pl->run_dense ? (pl->run_nt ? spmv::csr_runs_kernel<true, true> : spmv::csr_runs_kernel<true, false>)
-                                          : (pl->run_nt ? spmv::csr_runs_kernel<false, true> : spmv::csr_runs_kernel<false, false>);
-                hipLaunchKernelGGL(runs, grid, dim3(256), 0, s, pl->nrun_chunks, pl->rows, pl->cols, pl->d_run_chunks, pl->d_run_masks,
-                                   pl->run_pattern, a, x, y_in, y);
+                // The grid is whole groups of 8 workgroups (one per XCD); odd launches of a sweeping plan mirror the groups, so a chunk
+                // keeps its XCD and the multiply starts where the one before ended (internal.hpp).  A captured graph replays the
+                // direction it was captured with: harmless, the sums are the same and only the cache hits are lost.
+                const int groups = ((pl->nrun_chunks + spmv::kRunWaves - 1) / spmv::kRunWaves + 7) / 8;
+                const dim3 grid((unsigned) groups * 8u);
+                spmv::RunPattern pat = pl->run_pattern;
+                pat.mirror = pl->run_sweep && (pl->run_launches.fetch_add(1u, std::memory_order_relaxed) & 1u) ? groups : 0;
+                auto runs = run_kernel<false, true>(pl->run_yin_nt, pl->run_yout_nt);
+#ifdef SPMV_HIP_EXPERIMENTS
+                if (pl->run_dense)
+                    runs = pl->run_nt ? run_kernel<true, true>(pl->run_yin_nt, pl->run_yout_nt) : run_kernel<true, false>(pl->run_yin_nt, pl->run_yout_nt);
+                else if (!pl->run_nt)
+                    runs = run_kernel<false, false>(pl->run_yin_nt, pl->run_yout_nt);
+#endif
+                hipLaunchKernelGGL(runs, grid, dim3(256), 0, s, pl->nrun_chunks, pl->rows, pl->cols, pl->d_run_chunks, pl->d_run_masks, pat, a, x, y_in, y);
                 if (pl->nrun_rest > 0)
                     hipLaunchKernelGGL((spmv::csr_wavetile_kernel<512, true, true, false, 0, 0, false, false, false, true>), dim3((unsigned) ((pl->nrun_rest + 3) / 4)),
                                        dim3(256), 0, s, pl->nrun_rest, pl->d_tiles, p, j, pl->d_col16, a, x, y_in, y, pl->nnz, pl->cols, exact, pl->d_patterns,

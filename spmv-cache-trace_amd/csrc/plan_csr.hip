@@ -153,7 +153,8 @@ void drop_stencil_runs(spmv_hip_plan * pl)
     pl->d_run_masks = nullptr;
     pl->nrun_chunks = pl->nrun_rest = pl->run_len = pl->run_tiles = pl->run_masked_chunks = 0;
     pl->run_entries = 0;
-    pl->run_dense = pl->run_nt = false;
+    pl->run_dense = pl->run_nt = pl->run_sweep = false;
+    pl->run_yin_nt = pl->run_yout_nt = true;
 }
 
 // Stencil row runs (csr_runs.hpp).  Only for the launch that would otherwise multiply every tile with the plain default
@@ -179,13 +180,21 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
         return SPMV_HIP_OK;
     // plan-time switches of the experiments build (tools/ab.py): chunks cut from each range's first row instead of at multiples of
     // 128, no rows with missing positions in chunks, rows taken from the chunk number where the chunks are dense (off by default:
-    // it measured no faster), value loads without `nt`
+    // it measured no faster), value loads without `nt`, and the sweep and the y policies chosen below
     bool align = true, masked = true, early = false, nt = true;
+    // Round 10: odd launches sweep the chunks backwards, and y_in is read with the default policy where x and y
+    // together fit the 256 MiB Infinity Cache -- the next multiply then finds the end of y there.  Measured at three grid sizes
+    // only (x + y = 128, 256 and 512 MiB): the sweep won at the first two and cost nothing at the third; y_in without `nt` won
+    // at 256 MiB and lost 2.4 % at 512 MiB, so beyond the cache's size it keeps `nt`.  The y store keeps `nt` everywhere.
+    bool sweep = true, yin_nt = 8LL * ((long long) pl->rows + pl->cols) > (256LL << 20), yout_nt = true;
 #ifdef SPMV_HIP_EXPERIMENTS
     if (const char * v = std::getenv("SPMV_HIP_RUNS_ALIGN")) align = std::atoi(v) != 0;
     if (const char * v = std::getenv("SPMV_HIP_RUNS_MASKED")) masked = std::atoi(v) != 0;
     if (const char * v = std::getenv("SPMV_HIP_RUNS_EARLY")) early = std::atoi(v) != 0;
     if (const char * v = std::getenv("SPMV_HIP_RUNS_NT")) nt = std::atoi(v) != 0;
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_SWEEP")) sweep = std::atoi(v) != 0;
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_YIN_NT")) yin_nt = std::atoi(v) != 0;
+    if (const char * v = std::getenv("SPMV_HIP_RUNS_YOUT_NT")) yout_nt = std::atoi(v) != 0;
 #endif
     constexpr int L = spmv::kRunLen;
     const int ntiles = pl->ntiles;
@@ -431,6 +440,9 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
     pl->run_pattern = rp;
     pl->run_dense = dense;
     pl->run_nt = nt;
+    pl->run_sweep = sweep;
+    pl->run_yin_nt = yin_nt;
+    pl->run_yout_nt = yout_nt;
     return SPMV_HIP_OK;
 }
 
@@ -2408,7 +2420,8 @@ int spmv_hip_plan_info(const spmv_hip_plan * pl, int64_t * out, int n)
 {
     if (!pl || !out || n < 0)
         return fail(SPMV_HIP_ERR_INVALID, "plan/out null");
-    const int64_t v[43] = {pl->algorithm, pl->lanes_per_row, pl->workgroups, pl->nblk,
+    // [43]: 0 no runs, 1 csr_runs_kernel, + 4 where odd launches sweep the chunks backwards
+    const int64_t v[44] = {pl->algorithm, pl->lanes_per_row, pl->workgroups, pl->nblk,
                            pl->long_blocks, pl->rows, pl->nnz, (int64_t) pl->meta_bytes, pl->narrow_tiles,
                            pl->uniform_tiles, pl->shifted_tiles, pl->xwin_tiles, pl->blockwin_tiles,
                            pl->inner ? pl->inner->ntiles : 0, pl->streamed_bytes, pl->shifted_entries,
@@ -2420,8 +2433,9 @@ int spmv_hip_plan_info(const spmv_hip_plan * pl, int64_t * out, int n)
                            pl->stencil_mask_tiles, pl->stencil_mask_entries,
                            pl->nvalues > 0 ? 0 : pl->colshare_tiles, pl->nvalues > 0 ? 0 : pl->colshare_entries,
                            pl->colshare_tiles > 0 ? pl->block_hint : 0, pl->nrun_chunks, pl->run_tiles, pl->run_entries,
-                           pl->run_masked_chunks, pl->nrun_chunks > 0 ? pl->nrun_rest : 0};
-    for (int i = 0; i < n && i < 43; ++i)
+                           pl->run_masked_chunks, pl->nrun_chunks > 0 ? pl->nrun_rest : 0,
+                           pl->nrun_chunks > 0 ? 1 + (pl->run_sweep ? 4 : 0) : 0};
+    for (int i = 0; i < n && i < 44; ++i)
         out[i] = v[i];
     return SPMV_HIP_OK;
 }
