@@ -13,6 +13,9 @@
  * Guarantees: no atomics in the multiply, so two identical calls give identical bits; under SPMV_HIP_FLAG_EXACT_ORDER every
  * row is added left to right from +0.0 by one lane.  No load forms an address outside x[0, cols): the codes are the plan's
  * own.  One device only.  Callers detect the feature by the presence of the symbols.
+ *
+ * The plan is made from row_ptr and the columns alone, so it does not depend on the value type: spmv_hip_compact_f64.h
+ * multiplies the caller's fp64 values, unrounded, through the same plan object.
  */
 #ifndef SPMV_HIP_COMPACT_H
 #define SPMV_HIP_COMPACT_H

@@ -1,5 +1,6 @@
-// compact.hip -- include/spmv_hip_compact.h: y += fl32(A) x with the columns of a tile as 16-bit codes (a 3-bit window number and
-// a 13-bit offset from one of eight per-tile bases).  The tiles are f32values.hip's own (f32_plan.hpp): its descriptors as they
+// compact.hip -- include/spmv_hip_compact.h: y += fl32(A) x, and y += A x on the caller's fp64 values through the same plan
+// (include/spmv_hip_compact_f64.h), with the columns of a tile as 16-bit codes (a 3-bit window number and a 13-bit offset from one of
+// eight per-tile bases).  The tiles are f32values.hip's own (f32_plan.hpp): its descriptors as they
 // are, with the compact bits and the tile's first code quad added; the bases and the codes are made on the host by a few
 // threads, tile by tile; the kernel is csr_compact.hpp.
 #include "f32_plan.hpp"
@@ -11,6 +12,7 @@
 #include <new>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <utility>
 
 using namespace spmvi;
@@ -217,6 +219,38 @@ int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
     return SPMV_HIP_OK;
 }
 
+// spmv_hip_csr_spmv_c16 (V = float) and spmv_hip_csr_spmv_c16_f64 (V = double): the plan does not know the value type
+template <class V>
+int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const V * d_value,
+                 const double * d_x, double * d_y, void * stream)
+{
+    if (!pl)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    if (d_x && (const void *) d_x == (const void *) d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
+    if (pl->ntiles == 0) // rows, cols or nnz of zero
+        return SPMV_HIP_OK;
+    if (!d_row_ptr || !d_value || !d_x || !d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
+    if (!d_column_index && pl->wide_tiles > 0)
+        return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null and the plan has wide tiles, which read the 32-bit columns");
+    if (!aligned16(d_column_index) || !aligned16(d_value))
+        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
+    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
+    const bool x32 = (long long) pl->cols * 8 < (1LL << 32);
+    void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const double *, double *, int);
+    if constexpr (std::is_same<V, float>::value)
+        kernel = x32 ? spmv::csr_compact_kernel<true> : spmv::csr_compact_kernel<false>;
+    else
+        kernel = x32 ? spmv::csr_compact_f64_kernel<true> : spmv::csr_compact_f64_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
+                       d_y, exact);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -274,29 +308,13 @@ int spmv_hip_c16_plan_csr(spmv_hip_c16_plan ** plan, int32_t rows, int32_t cols,
 int spmv_hip_csr_spmv_c16(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
                           const double * d_x, double * d_y, void * stream)
 {
-    if (!pl)
-        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
-    if (d_x && (const void *) d_x == (const void *) d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
-    if (pl->ntiles == 0) // rows, cols or nnz of zero
-        return SPMV_HIP_OK;
-    if (!d_row_ptr || !d_value || !d_x || !d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
-    if (!d_column_index && pl->wide_tiles > 0)
-        return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null and the plan has wide tiles, which read the 32-bit columns");
-    if (!aligned16(d_column_index) || !aligned16(d_value))
-        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
-    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
-    if ((long long) pl->cols * 8 < (1LL << 32))
-        hipLaunchKernelGGL(spmv::csr_compact_kernel<true>, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr,
-                           d_column_index, d_value, d_x, d_y, exact);
-    else
-        hipLaunchKernelGGL(spmv::csr_compact_kernel<false>, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr,
-                           d_column_index, d_value, d_x, d_y, exact);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream);
+}
+
+int spmv_hip_csr_spmv_c16_f64(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value,
+                              const double * d_x, double * d_y, void * stream)
+{
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream);
 }
 
 int spmv_hip_c16_plan_verify(const spmv_hip_c16_plan * pl, const int32_t * d_column_index, int64_t * mismatches, void * stream)
@@ -388,6 +406,42 @@ int spmv_hip_upload_csr_compact(spmv_hip_ctx * c, int32_t rows, int32_t cols, in
     c->nnz = nnz;
     c->bytes += c->c16_plan->device_bytes;
     c->format = 8;
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_upload_csr_compact_f64(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
+                                    const int32_t * column_index, const double * value)
+{
+    if (!c)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
+    if (c->multi)
+        return fail(SPMV_HIP_ERR_STATE, "the compact multiply runs on one device (a context of spmv_hip_create)");
+    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
+    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
+    // everything that can refuse the matrix happens before anything is freed or copied
+    int rc = f32_check_host(rows, cols, row_ptr, flags);
+    if (rc != 0)
+        return rc;
+    if (row_ptr[rows] != nnz)
+        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
+    HostPlan hp;
+    if ((rc = plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0) // (... the columns here)
+        return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_ctx_matrix(c);
+    if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
+        return rc;
+    // the values as they are (d_val); only wide tiles read 32-bit columns
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr,
+                             column_index, c->c16_plan->wide_tiles > 0, value, false)) != 0)
+        return rc;
+    c->rows = rows;
+    c->cols = cols;
+    c->nnz = nnz;
+    c->bytes += c->c16_plan->device_bytes;
+    c->format = 9;
     return SPMV_HIP_OK;
 }
 

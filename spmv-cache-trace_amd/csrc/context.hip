@@ -803,6 +803,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
     case 6: rc = spmv_hip_csr_spmv_t(c->tr_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
     case 7: rc = spmv_hip_csr_spmv_f32(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
     case 8: rc = spmv_hip_csr_spmv_c16(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
+    case 9: rc = spmv_hip_csr_spmv_c16_f64(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
     case 2:
         rc = c->as_csr ? csr_run() : ctx_coo_run(c, c->nnz, c->d_idx, c->d_col, c->d_val);
         break;
@@ -952,11 +953,11 @@ int spmv_hip_ctx_info(spmv_hip_ctx * c, int64_t * out, int n)
         v[6] = fi[11];
         v[15] = fi[8];
     }
-    if (c->c16_plan) { // format 8: workgroups and streamed bytes of the compact plan
+    if (c->c16_plan) { // formats 8 and 9: workgroups and streamed bytes of the compact plan (format 9: with 8-byte values)
         int64_t ci[SPMV_HIP_C16_INFO] = {0};
         spmv_hip_c16_plan_info(c->c16_plan, ci, SPMV_HIP_C16_INFO);
         v[6] = ci[4];
-        v[15] = ci[19];
+        v[15] = ci[19] + (c->format == 9 && ci[19] ? 4 * ci[2] : 0);
     }
     if (c->d_prow)
         v[14] += c->coo_panel_blocks; // COO (part) in column panels: workgroups per panel

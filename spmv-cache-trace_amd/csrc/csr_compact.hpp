@@ -6,6 +6,9 @@
 // whose columns fit ONE window -- every 2-D mesh, stencil and band -- adds its base to the scalar x pointer instead and gathers
 // at the code itself: no table read, no add.  The wave-uniform compact bit of the descriptor sends WIDE tiles to the caller's
 // 32-bit columns (WideSource).  No atomics, no workgroup barrier.
+//
+// csr_compact_f64_kernel is y += A x: the same tile over the caller's fp64 values (ValueQuad<double>: a quad is two
+// 16-byte loads, so per lane four value loads and two code loads go out before anything waits; nothing is widened).
 #pragma once
 
 #include "csr_f32values.hpp"
@@ -54,8 +57,8 @@ struct CompactSource {
 
     __device__ __forceinline__ int at(int k) const { return compact ? CodeColumns<false>{cz, tab}.at(k) : wide.at(k); }
 
-    template <int QUADS, bool X32>
-    __device__ __forceinline__ void products(double * prod, const float * __restrict__ at, const double * __restrict__ x, int kb,
+    template <int QUADS, bool X32, class V>
+    __device__ __forceinline__ void products(double * prod, const V * __restrict__ at, const double * __restrict__ x, int kb,
                                              int last, int lane) const
     {
         if (!compact)
@@ -65,18 +68,19 @@ struct CompactSource {
         else
             quad_products<QUADS, X32>(prod, CodeColumns<false>{cz + kb, tab}, at, x, last, lane);
     }
-    template <bool X32>
-    __device__ __forceinline__ double long_row(const float * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
+    template <bool X32, class V>
+    __device__ __forceinline__ double long_row(const V * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
     {
         return compact ? long_row_sum_f32<X32>(CodeColumns<false>{cz, tab}, a, x, k0, k1, lane) : wide.long_row<X32>(a, x, k0, k1, lane);
     }
 };
 
-template <bool X32>
-__global__ __launch_bounds__(256, 8) void csr_compact_kernel(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
-                                                             const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
-                                                             const int32_t * __restrict__ j, const float * __restrict__ a,
-                                                             const double * __restrict__ x, double * y, int exact_order)
+// One wave of either kernel below: its tile's window table into the wave's LDS slot, then the tile over V values.
+template <bool X32, class V>
+__device__ __forceinline__ void compact_wave(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
+                                             const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
+                                             const int32_t * __restrict__ j, const V * __restrict__ a, const double * __restrict__ x,
+                                             double * y, int exact_order)
 {
     __shared__ __attribute__((aligned(16))) double prod_all[4][kF32Tile + 4];
     __shared__ int tab_all[4][8];
@@ -99,6 +103,25 @@ __global__ __launch_bounds__(256, 8) void csr_compact_kernel(int ntiles, const i
     // the tile's codes start at quad t.w with the slot of entry k0 & ~3
     const CompactSource src{compact, (t.meta & kC16MetaOneWindow) != 0, codes + 4 * (size_t) (unsigned) t.w - (t.k0 & ~3), tab, base0, WideSource{j}};
     f32_tile<X32>(prod_all[wave], t, src, p, a, x, y, exact_order);
+}
+
+template <bool X32>
+__global__ __launch_bounds__(256, 8) void csr_compact_kernel(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
+                                                             const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
+                                                             const int32_t * __restrict__ j, const float * __restrict__ a,
+                                                             const double * __restrict__ x, double * y, int exact_order)
+{
+    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
+}
+
+// y += A x: the fp64 values of the caller beside the codes
+template <bool X32>
+__global__ __launch_bounds__(256, 8) void csr_compact_f64_kernel(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
+                                                                 const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
+                                                                 const int32_t * __restrict__ j, const double * __restrict__ a,
+                                                                 const double * __restrict__ x, double * y, int exact_order)
+{
+    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
 }
 
 // spmv_hip_c16_plan_verify: a wave per tile; every entry of a compact tile decoded and compared with the caller's column

@@ -11,6 +11,10 @@
 // of a quad come from -- load(o): the stored quad at offset o, columns(quad): its four column indices, at(k): the column at
 // offset k (WideColumns here, CodeColumns<ONE> there).  A kernel's SOURCE (WideSource here, CompactSource there) counts from
 // entry 0 and runs the two loops that read quads, quad_products and long_row_sum_f32, on the columns it chooses.
+//
+// The tile also has a VALUE TYPE V: float for the two multiplies of fl32(A), double for csr_compact_f64_kernel
+// (y += A x on the caller's fp64 values beside the 16-bit codes, 10 bytes per entry).  Only ValueQuad<V> differs: how the four
+// values of a quad are loaded and that a float is widened before it is multiplied.
 #pragma once
 
 #include "tile_common.hpp"
@@ -24,31 +28,59 @@ constexpr int kF32TileRows = 64;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
+// The four values of a quad as they are stored, V = float or double, and each of them as the fp64 factor of its product.
+// Floats: one 16-byte load, widened where they are multiplied (v_cvt_f64_f32: exact).  Doubles: 32 bytes as TWO 16-byte loads,
+// so the array need only be 16-byte aligned (a 4-aligned entry of it is then 16-, not 32-byte aligned); nothing is widened.
+template <class V>
+struct ValueQuad;
+template <>
+struct ValueQuad<float> {
+    v4f q;
+    static __device__ __forceinline__ ValueQuad load(const float * __restrict__ a) { return ValueQuad{*reinterpret_cast<const v4f *>(a)}; }
+    __device__ __forceinline__ double x() const { return (double) q.x; }
+    __device__ __forceinline__ double y() const { return (double) q.y; }
+    __device__ __forceinline__ double z() const { return (double) q.z; }
+    __device__ __forceinline__ double w() const { return (double) q.w; }
+};
+template <>
+struct ValueQuad<double> {
+    v2d lo, hi;
+    static __device__ __forceinline__ ValueQuad load(const double * __restrict__ a)
+    {
+        const v2d * q = reinterpret_cast<const v2d *>(a);
+        return ValueQuad{q[0], q[1]};
+    }
+    __device__ __forceinline__ double x() const { return lo.x; }
+    __device__ __forceinline__ double y() const { return lo.y; }
+    __device__ __forceinline__ double z() const { return hi.x; }
+    __device__ __forceinline__ double w() const { return hi.y; }
+};
+
 // tile_products_wide's rules: lanes past the tile's end re-read its last quad; entries in front of the tile that share its
 // first quad are multiplied and never read back.  cols and at count from the tile's first quad.  Every lane works out its
 // columns (the lanes past the tile's end hold its last quad's); only the gathers are predicated.
-template <int QUADS, bool X32, class Columns>
-__device__ __forceinline__ void quad_products(double * prod, const Columns cols, const float * __restrict__ at,
+template <int QUADS, bool X32, class Columns, class V>
+__device__ __forceinline__ void quad_products(double * prod, const Columns cols, const V * __restrict__ at,
                                               const double * __restrict__ x, int last, int lane)
 {
     typename Columns::quad c[QUADS];
-    v4f v[QUADS];
+    ValueQuad<V> v[QUADS];
 #pragma unroll
     for (int q = 0; q < QUADS; ++q) {
         int o = 256 * q + 4 * lane;
         o = o < last ? o : last;
         c[q] = cols.load(o);
-        v[q] = *reinterpret_cast<const v4f *>(at + o);
+        v[q] = ValueQuad<V>::load(at + o);
     }
 #pragma unroll
     for (int q = 0; q < QUADS; ++q) {
         const int o = 256 * q + 4 * lane;
         const v4i j = cols.columns(c[q]);
         if (o <= last) {
-            const double q0 = (double) v[q].x * gather_x<X32>(x, j.x);
-            const double q1 = (double) v[q].y * gather_x<X32>(x, j.y);
-            const double q2 = (double) v[q].z * gather_x<X32>(x, j.z);
-            const double q3 = (double) v[q].w * gather_x<X32>(x, j.w);
+            const double q0 = v[q].x() * gather_x<X32>(x, j.x);
+            const double q1 = v[q].y() * gather_x<X32>(x, j.y);
+            const double q2 = v[q].z() * gather_x<X32>(x, j.z);
+            const double q3 = v[q].w() * gather_x<X32>(x, j.w);
             v2d * dst = reinterpret_cast<v2d *>(prod + o);
             dst[0] = v2d{q0, q1};
             dst[1] = v2d{q2, q3};
@@ -59,8 +91,8 @@ __device__ __forceinline__ void quad_products(double * prod, const Columns cols,
 // long_row_sum (tile_common.hpp) over float values: the 4-aligned interior [ka, kz) in quads, two per lane and step in
 // flight, four accumulators per lane; the up to three entries in front of ka and behind kz by single lanes.  Nothing is read
 // outside [k0, k1).  cols and a count from entry 0.
-template <bool X32, class Columns>
-__device__ __forceinline__ double long_row_sum_f32(const Columns cols, const float * __restrict__ a, const double * __restrict__ x,
+template <bool X32, class Columns, class V>
+__device__ __forceinline__ double long_row_sum_f32(const Columns cols, const V * __restrict__ a, const double * __restrict__ x,
                                                    int k0, int k1, int lane)
 {
     double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
@@ -78,19 +110,19 @@ __device__ __forceinline__ double long_row_sum_f32(const Columns cols, const flo
         const bool two = o + 4 * kWave < kz;
         const int o2 = two ? o + 4 * kWave : o;
         const typename Columns::quad ca = cols.load(o), cb = cols.load(o2);
-        const v4f va = *reinterpret_cast<const v4f *>(a + o), vb = *reinterpret_cast<const v4f *>(a + o2);
+        const ValueQuad<V> va = ValueQuad<V>::load(a + o), vb = ValueQuad<V>::load(a + o2);
         const v4i ja = cols.columns(ca), jb = cols.columns(cb);
         const double xa0 = gather_x<X32>(x, ja.x), xa1 = gather_x<X32>(x, ja.y), xa2 = gather_x<X32>(x, ja.z), xa3 = gather_x<X32>(x, ja.w);
         const double xb0 = gather_x<X32>(x, jb.x), xb1 = gather_x<X32>(x, jb.y), xb2 = gather_x<X32>(x, jb.z), xb3 = gather_x<X32>(x, jb.w);
-        z0 += (double) va.x * xa0;
-        z1 += (double) va.y * xa1;
-        z2 += (double) va.z * xa2;
-        z3 += (double) va.w * xa3;
+        z0 += va.x() * xa0;
+        z1 += va.y() * xa1;
+        z2 += va.z() * xa2;
+        z3 += va.w() * xa3;
         if (two) {
-            z0 += (double) vb.x * xb0;
-            z1 += (double) vb.y * xb1;
-            z2 += (double) vb.z * xb2;
-            z3 += (double) vb.w * xb3;
+            z0 += vb.x() * xb0;
+            z1 += vb.y() * xb1;
+            z2 += vb.z() * xb2;
+            z3 += vb.w() * xb3;
         }
     }
     return group_sum<kWave>((z0 + z1) + (z2 + z3));
@@ -110,14 +142,14 @@ struct WideSource {
     const int32_t * __restrict__ j;
     __device__ __forceinline__ int at(int k) const { return j[k]; }
     // the products of the tile whose first quad starts at entry kb (at = a + kb)
-    template <int QUADS, bool X32>
-    __device__ __forceinline__ void products(double * prod, const float * __restrict__ at, const double * __restrict__ x, int kb,
+    template <int QUADS, bool X32, class V>
+    __device__ __forceinline__ void products(double * prod, const V * __restrict__ at, const double * __restrict__ x, int kb,
                                              int last, int lane) const
     {
         quad_products<QUADS, X32>(prod, WideColumns{j + kb}, at, x, last, lane);
     }
-    template <bool X32>
-    __device__ __forceinline__ double long_row(const float * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
+    template <bool X32, class V>
+    __device__ __forceinline__ double long_row(const V * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
     {
         return long_row_sum_f32<X32>(WideColumns{j}, a, x, k0, k1, lane);
     }
@@ -143,9 +175,9 @@ __device__ __forceinline__ F32Tile load_f32_tile(const int4 * __restrict__ desc,
 }
 
 // One tile by one wave; prod is the wave's LDS slice (kF32Tile + 4 doubles), src the kernel's column source.
-template <bool X32, class Source>
+template <bool X32, class Source, class V>
 __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const Source src, const int32_t * __restrict__ p,
-                                         const float * __restrict__ a, const double * __restrict__ x, double * y, int exact_order)
+                                         const V * __restrict__ a, const double * __restrict__ x, double * y, int exact_order)
 {
     constexpr int TILE = kF32Tile, QUADS = TILE / 256;
     const int lane = (int) __lane_id();

@@ -22,6 +22,7 @@
 #include "spmv_hip_transpose.h"
 #include "spmv_hip_f32values.h"
 #include "spmv_hip_compact.h"
+#include "spmv_hip_compact_f64.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -215,6 +216,7 @@ struct spmv_hip_ctx {
                     // 6 csr multiplied transposed (rows / cols are those of the operator that runs, A'),
                     // 7 csr with the values as 4-byte floats (d_val32; no fp64 values are kept),
                     // 8 ... and 16-bit column codes in the plan (d_col only where the plan has wide tiles)
+                    // 9 csr with the fp64 values as they are (d_val) and 16-bit column codes in the plan (d_col as for 8)
     int32_t rows = 0, cols = 0, nnz = 0, row_length = 0, nnz2 = 0;
     int csr_algorithm = SPMV_HIP_CSR_AUTO;
     int csr_lanes = 0;
@@ -223,7 +225,7 @@ struct spmv_hip_ctx {
     spmv_hip_tr_plan * tr_plan = nullptr;   // format 6 (transpose.hip)
     spmv_hip_f32_plan * f32_plan = nullptr; // format 7 (f32values.hip)
     float * d_val32 = nullptr;              // ... its values
-    spmv_hip_c16_plan * c16_plan = nullptr; // format 8 (compact.hip; its values are d_val32 too)
+    spmv_hip_c16_plan * c16_plan = nullptr; // formats 8 (compact.hip; its values are d_val32 too) and 9 (... d_val)
     // block vectors of spmv_hip_run_block (multivec.hip; format 1 only): X (cols x block_k) and Y (rows x block_k), row-major,
     // apart from d_x / d_y; the plan is made on the first run_block after the matrix or k changed
     spmv_hip_mv_plan * mv_plan = nullptr;

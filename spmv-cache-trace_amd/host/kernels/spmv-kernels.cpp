@@ -10,6 +10,7 @@
 #include "spmv_hip_transpose.h"
 #include "spmv_hip_f32values.h"
 #include "spmv_hip_compact.h"
+#include "spmv_hip_compact_f64.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -650,6 +651,57 @@ private:
     double max_rounding = 0.0;
 };
 
+// --compact=f64: the 16-bit window codes of --compact beside the fp64 values as they are: y += A x, nothing rounded
+class hip_csr_compact_f64_spmv_kernel : public hip_kernel_base
+{
+public:
+    using hip_kernel_base::hip_kernel_base;
+    void init(TraceConfig const &, std::ostream & o, bool verbose) override
+    {
+        auto const t0 = std::chrono::steady_clock::now();
+        guarded_init(matrix_path, [&] {
+            A = load_csr(matrix_path, options, o, verbose);
+            x.assign((std::size_t) A.columns, 1.0);
+            y.assign((std::size_t) A.rows, 0.0);
+        });
+        auto const t1 = std::chrono::steady_clock::now();
+        if (options.num_gpus == 1)
+            options.num_gpus = 0; // --gpus 1: the one-device context this upload needs
+        create_context();
+        check(spmv_hip_upload_csr_compact_f64(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(),
+                                              A.column_index.data(), A.value.data()), "upload_csr_compact_f64");
+        std::int64_t info[SPMV_HIP_C16_INFO] = {0};
+        check(spmv_hip_c16_plan_preview(A.rows, A.columns, A.row_ptr.data(), A.column_index.data(),
+                                        options.hip_flags & SPMV_HIP_FLAG_EXACT_ORDER, info, SPMV_HIP_C16_INFO, nullptr, 0, nullptr),
+              "c16_plan_preview");
+        compact_tiles = info[6];
+        wide_tiles = info[7];
+        compact_entries = info[9];
+        streamed = info[19] ? info[19] + 4 * info[2] : 0;
+        init_load_seconds = std::chrono::duration<double>(t1 - t0).count();
+        init_upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    }
+    std::string name() const override { return "hip-csr-spmv-compact-f64"; }
+    std::ostream & print(std::ostream & o) const override
+    {
+        print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
+        o << ",\n\"value_bytes\": 8,\n\"compact_tiles\": " << compact_tiles << ",\n\"wide_tiles\": " << wide_tiles
+          << ",\n\"streamed_bytes\": " << streamed;
+        return print_device(o) << "\n}";
+    }
+
+    double flops_per_run() const override { return 2.0 * A.num_entries; }
+    double bytes_per_run() const override
+    {
+        double const nnz = A.row_ptr[(std::size_t) A.rows];
+        return 10.0 * compact_entries + 12.0 * (nnz - compact_entries) + 4.0 * (A.rows + 1.0) + 16.0 * A.rows + 8.0 * A.columns;
+    }
+
+private:
+    csr_matrix::Matrix A;
+    long long compact_tiles = 0, wide_tiles = 0, compact_entries = 0, streamed = 0;
+};
+
 // --transpose: A stays on the device as it is stored and every run adds A' x to y (x has rows entries, y has columns): no
 // transposed copy of the matrix is made, on the host or on the device
 class hip_csr_transposed_spmv_kernel : public hip_kernel_base
@@ -865,6 +917,7 @@ std::unique_ptr<Kernel> make_spmv_kernel(SpmvFormat format, bool hip, std::strin
         if (hip && opt.symmetric) return std::make_unique<hip_csr_symmetric_spmv_kernel>(path, opt);
         if (hip && opt.vectors > 0) return std::make_unique<hip_csr_multivec_spmv_kernel>(path, opt);
         if (hip && opt.transpose) return std::make_unique<hip_csr_transposed_spmv_kernel>(path, opt);
+        if (hip && opt.compact == 3) return std::make_unique<hip_csr_compact_f64_spmv_kernel>(path, opt);
         if (hip && opt.compact) return std::make_unique<hip_csr_compact_spmv_kernel>(path, opt);
         if (hip && opt.f32_values) return std::make_unique<hip_csr_f32values_spmv_kernel>(path, opt);
         if (hip) return std::make_unique<hip_csr_spmv_kernel>(path, opt);

@@ -217,7 +217,8 @@ error_t parse_option(int key, char * arg, argp_state * state)
     case key_compact:
         if (!arg || !std::strcmp(arg, "round")) a.spmv.compact = 1;
         else if (!std::strcmp(arg, "exact")) a.spmv.compact = 2;
-        else argp_error(state, "compact: expected 'round' (the default) or 'exact'");
+        else if (!std::strcmp(arg, "f64")) a.spmv.compact = 3;
+        else argp_error(state, "compact: expected 'round' (the default) or 'exact', or 'f64'");
         break;
     case ARGP_KEY_END:
         if (a.list_perf_events)
@@ -232,8 +233,11 @@ error_t parse_option(int key, char * arg, argp_state * state)
             if (a.spmv.vectors > 0)
                 argp_error(state, "--compact cannot be combined with --vectors: there is no multi-vector kernel over 16-bit column codes");
             if (a.spmv.f32_values)
-                argp_error(state, "--compact cannot be combined with --f32-values: --compact stores the values as floats already "
-                                  "(--compact=exact refuses values that are not floats)");
+                argp_error(state, a.spmv.compact == 3
+                               ? "--compact=f64 cannot be combined with --f32-values: it multiplies the fp64 values as they are "
+                                 "(--compact stores them as floats)"
+                               : "--compact cannot be combined with --f32-values: --compact stores the values as floats already "
+                                 "(--compact=exact refuses values that are not floats)");
             if (a.kernel_type != KernelType::spmv || a.format != SpmvFormat::csr)
                 argp_error(state, "--compact needs the CSR kernel on the GPU (--spmv-format hip-csr or --csr PATH): "
                                   "there is no COO, ELLPACK or hybrid kernel over 16-bit column codes");
@@ -402,11 +406,13 @@ int main(int argc, char ** argv)
          "(8 instead of 12 bytes per stored entry).  round (default): values are rounded to the nearest float and the JSON "
          "document says how many and by how much; exact: a matrix with values that are not floats already is refused.  --check "
          "compares with the CPU CSR kernel on the values rounded on the host", 2},
-        {"compact", key_compact, "round|exact", OPTION_ARG_OPTIONAL,
+        {"compact", key_compact, "round|exact|f64", OPTION_ARG_OPTIONAL,
          "EXTENSION (hip-csr, one device): --f32-values with the columns of a tile streamed as 16-bit codes, a 3-bit window number "
          "and a 13-bit offset from one of eight per-tile bases (6 instead of 8 bytes per stored entry); tiles that need more "
          "than eight windows keep their 32-bit columns, and the JSON document counts both kinds.  round (default) and exact are "
-         "those of --f32-values.  --check compares with the CPU CSR kernel on the values rounded on the host", 2},
+         "those of --f32-values.  --check compares with the CPU CSR kernel on the values rounded on the host.  f64: the same "
+         "16-bit codes beside the fp64 values as they are (10 instead of 12 bytes per stored entry, nothing is rounded: "
+         "kernel hip-csr-spmv-compact-f64); --check compares with the CPU CSR kernel on the unrounded values", 2},
         {"vectors", key_vectors, "K", 0,
          "EXTENSION (hip-csr, one device): Y += A X for K = 1 ... 16 vectors in one multiply, every stored entry read once; column c "
          "of X is x scaled by c + 1.  Flops count 2 nnz K; --check compares every column with the CPU CSR kernel", 2},
@@ -583,7 +589,9 @@ int main(int argc, char ** argv)
                 ref_options.transpose_on_host = true;
             }
             // (--f32-values: the values rounded on the host by static_cast<float> -- an independent path to the same operator)
-            if (args.spmv.f32_values || args.spmv.compact) {
+            bool const rounded = args.spmv.f32_values || args.spmv.compact == 1 || args.spmv.compact == 2; // (--compact=f64 rounds nothing)
+            ref_options.compact = 0;
+            if (rounded) {
                 ref_options.f32_values = 0;
                 ref_options.compact = 0;
                 ref_options.round_values_on_host = true;
@@ -617,7 +625,7 @@ int main(int argc, char ** argv)
             parity = ",\n\"parity\": {\"against\": \"csr-spmv (CPU, 1 thread)" +
                 std::string(args.spmv.symmetric ? " on the expanded matrix (expand_symmetry)" : "") +
                 std::string(args.spmv.transpose ? " on the matrix transposed on the host" : "") +
-                std::string(args.spmv.f32_values || args.spmv.compact ? " on the values rounded to float on the host" : "") +
+                std::string(rounded ? " on the values rounded to float on the host" : "") +
                 (args.spmv.vectors > 0 ? ", every one of the " + std::to_string(k) + " columns" : std::string()) + ", " +
                 std::to_string(args.profile + 1) + " accumulating runs\", \"max_relative_error\": ";
             char buf[64];

@@ -1,5 +1,5 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
-spmv_hip_transpose.h, spmv_hip_f32values.h and spmv_hip_compact.h (the C ABI of libspmv_hip.so).
+spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h and spmv_hip_compact_f64.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -23,7 +23,8 @@ elif os.environ.get("SPMV_HIP_EXPERIMENTS", "").endswith(".so"):  # an ablation 
 HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
-                                          "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h")]
+                                          "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
+                                          "spmv_hip_compact_f64.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -140,10 +141,12 @@ SIGNATURES = {
     "spmv_hip_c16_plan_preview": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_uint, _vp, C.c_int, _vp, C.c_int64, _vp]),
     "spmv_hip_c16_plan_csr": (C.c_int, [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, _vp, C.c_uint, _vp]),
     "spmv_hip_csr_spmv_c16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_csr_spmv_c16_f64": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_c16_plan_verify": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
     "spmv_hip_c16_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
     "spmv_hip_c16_plan_destroy": (None, [_vp]),
     "spmv_hip_upload_csr_compact": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
+    "spmv_hip_upload_csr_compact_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
 }
 
 
@@ -341,6 +344,17 @@ class Context:
             col, val = _EMPTY_I32, _EMPTY_F64
         check(self.lib.spmv_hip_upload_csr_compact(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data,
                                                    1 if allow_rounding else 0))
+        self.rows, self.cols = rows, cols
+
+    def upload_csr_compact_f64(self, rows, cols, row_ptr, col, val):
+        """upload_csr with the columns of a tile as 16-bit window codes in the plan and the fp64 values as they are (10 bytes per
+        stored entry, nothing rounded): every run adds A x to y; no 32-bit columns are kept where the plan has no wide tile
+        (include/spmv_hip_compact_f64.h)."""
+        row_ptr, col, val = _i32(row_ptr), _i32(col), _f64(val)
+        nnz = int(row_ptr[rows]) if len(row_ptr) > rows >= 0 else -1
+        if len(col) == 0:
+            col, val = _EMPTY_I32, _EMPTY_F64
+        check(self.lib.spmv_hip_upload_csr_compact_f64(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data))
         self.rows, self.cols = rows, cols
 
     def set_x(self, x):
@@ -757,6 +771,10 @@ class C16Plan:
         """y += fl32(A) x; raw device addresses, d_val32 a float array, d_x != d_y; d_col may be 0 / None where the plan has no
         wide tile."""
         check(self.lib.spmv_hip_csr_spmv_c16(self.h, d_row_ptr, d_col or None, d_val32, d_x, d_y, stream))
+
+    def spmv_f64(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
+        """y += A x through the same plan; d_val an fp64 array (16-byte aligned), otherwise as spmv."""
+        check(self.lib.spmv_hip_csr_spmv_c16_f64(self.h, d_row_ptr, d_col or None, d_val, d_x, d_y, stream))
 
     def verify(self, d_col, stream=0):
         """How many entries of compact tiles decode to a column other than d_col's (the content guard)."""
