@@ -1,5 +1,5 @@
-// compact.hip -- include/spmv_hip_compact.h: y += fl32(A) x, and y += A x on the caller's fp64 values through the same plan
-// (include/spmv_hip_compact_f64.h), with the columns of a tile as 16-bit codes (a 3-bit window number and a 13-bit offset from one of
+// compact.hip -- include/spmv_hip_compact.h: y += fl32(A) x, y += A x on the caller's fp64 values through the same plan
+// (include/spmv_hip_compact_f64.h) and y <- fl32(y + fl32(A) x) on float x and y (include/spmv_hip_compact_f32xy.h), with the columns of a tile as 16-bit codes (a 3-bit window number and a 13-bit offset from one of
 // eight per-tile bases).  The tiles are f32values.hip's own (f32_plan.hpp): its descriptors as they
 // are, with the compact bits and the tile's first code quad added; the bases and the codes are made on the host by a few
 // threads, tile by tile; the kernel is csr_compact.hpp.
@@ -219,10 +219,11 @@ int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
     return SPMV_HIP_OK;
 }
 
-// spmv_hip_csr_spmv_c16 (V = float) and spmv_hip_csr_spmv_c16_f64 (V = double): the plan does not know the value type
-template <class V>
+// spmv_hip_csr_spmv_c16 (V = float, T = double), spmv_hip_csr_spmv_c16_f64 (V = double) and spmv_hip_csr_spmv_c16_f32xy (V = T =
+// float): the plan knows neither the value type nor the vectors' element type
+template <class V, class T>
 int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const V * d_value,
-                 const double * d_x, double * d_y, void * stream)
+                 const T * d_x, T * d_y, void * stream)
 {
     if (!pl)
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
@@ -236,18 +237,68 @@ int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const 
         return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null and the plan has wide tiles, which read the 32-bit columns");
     if (!aligned16(d_column_index) || !aligned16(d_value))
         return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
+    if constexpr (std::is_same<T, float>::value) // (the kernel reads and writes x and y one element at a time)
+        if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_y)) & 3u)
+            return fail(SPMV_HIP_ERR_ALIGN, "d_x and d_y must be 4-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
     const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
-    const bool x32 = (long long) pl->cols * 8 < (1LL << 32);
-    void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const double *, double *, int);
-    if constexpr (std::is_same<V, float>::value)
+    const bool x32 = (long long) pl->cols * (long long) sizeof(T) < (1LL << 32);
+    void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, T *, int);
+    if constexpr (std::is_same<T, float>::value)
+        kernel = x32 ? spmv::csr_compact_f32xy_kernel<true> : spmv::csr_compact_f32xy_kernel<false>;
+    else if constexpr (std::is_same<V, float>::value)
         kernel = x32 ? spmv::csr_compact_kernel<true> : spmv::csr_compact_kernel<false>;
     else
         kernel = x32 ? spmv::csr_compact_f64_kernel<true> : spmv::csr_compact_f64_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
                        d_y, exact);
     HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
+// spmv_hip_upload_csr_compact (format 8) and spmv_hip_upload_csr_compact_f32xy (format 10: float_vectors)
+int upload_compact_floats(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr, const int32_t * column_index,
+                          const double * value, int allow_rounding, bool float_vectors)
+{
+    if (!c)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
+    if (c->multi)
+        return fail(SPMV_HIP_ERR_STATE, "the compact multiply runs on one device (a context of spmv_hip_create)");
+    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
+    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
+    // everything that can refuse the matrix happens before anything is freed or copied
+    int rc = f32_check_host(rows, cols, row_ptr, flags);
+    if (rc != 0)
+        return rc;
+    if (row_ptr[rows] != nnz)
+        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
+    HostPlan hp;
+    if ((rc = plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0) // (... the columns here)
+        return rc;
+    std::vector<float> narrow;
+    try {
+        narrow.resize((size_t) nnz);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "compact upload: host memory");
+    }
+    if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
+        return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_ctx_matrix(c);
+    if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
+        return rc;
+    // only wide tiles read 32-bit columns
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr,
+                             column_index, c->c16_plan->wide_tiles > 0, narrow.data(), true, float_vectors)) != 0)
+        return rc;
+    c->rows = rows;
+    c->cols = cols;
+    c->nnz = nnz;
+    c->bytes += c->c16_plan->device_bytes;
+    c->format = float_vectors ? 10 : 8;
     return SPMV_HIP_OK;
 }
 
@@ -317,6 +368,12 @@ int spmv_hip_csr_spmv_c16_f64(const spmv_hip_c16_plan * pl, const int32_t * d_ro
     return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream);
 }
 
+int spmv_hip_csr_spmv_c16_f32xy(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                                const float * d_x, float * d_y, void * stream)
+{
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream);
+}
+
 int spmv_hip_c16_plan_verify(const spmv_hip_c16_plan * pl, const int32_t * d_column_index, int64_t * mismatches, void * stream)
 {
     if (!pl || !mismatches)
@@ -368,45 +425,13 @@ void spmv_hip_c16_plan_destroy(spmv_hip_c16_plan * pl)
 int spmv_hip_upload_csr_compact(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
                                 const int32_t * column_index, const double * value, int allow_rounding)
 {
-    if (!c)
-        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
-    if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "the compact multiply runs on one device (a context of spmv_hip_create)");
-    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
-    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
-    // everything that can refuse the matrix happens before anything is freed or copied
-    int rc = f32_check_host(rows, cols, row_ptr, flags);
-    if (rc != 0)
-        return rc;
-    if (row_ptr[rows] != nnz)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
-    HostPlan hp;
-    if ((rc = plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0) // (... the columns here)
-        return rc;
-    std::vector<float> narrow;
-    try {
-        narrow.resize((size_t) nnz);
-    } catch (std::bad_alloc const &) {
-        return fail(SPMV_HIP_ERR_ALLOC, "compact upload: host memory");
-    }
-    if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
-        return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_ctx_matrix(c);
-    if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
-        return rc;
-    // only wide tiles read 32-bit columns
-    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr,
-                             column_index, c->c16_plan->wide_tiles > 0, narrow.data(), true)) != 0)
-        return rc;
-    c->rows = rows;
-    c->cols = cols;
-    c->nnz = nnz;
-    c->bytes += c->c16_plan->device_bytes;
-    c->format = 8;
-    return SPMV_HIP_OK;
+    return upload_compact_floats(c, rows, cols, nnz, row_ptr, column_index, value, allow_rounding, false);
+}
+
+int spmv_hip_upload_csr_compact_f32xy(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
+                                      const int32_t * column_index, const double * value, int allow_rounding)
+{
+    return upload_compact_floats(c, rows, cols, nnz, row_ptr, column_index, value, allow_rounding, true);
 }
 
 int spmv_hip_upload_csr_compact_f64(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,

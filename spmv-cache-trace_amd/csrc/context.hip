@@ -37,6 +37,9 @@ void free_ctx_matrix(spmv_hip_ctx * c)
         (void) hipFree(c->d_val32);
         c->d_val32 = nullptr;
     }
+    if (c->d_x32) (void) hipFree(c->d_x32);
+    if (c->d_y32) (void) hipFree(c->d_y32);
+    c->d_x32 = c->d_y32 = nullptr;
     if (c->mv_plan) {
         spmv_hip_mv_plan_destroy(c->mv_plan);
         c->mv_plan = nullptr;
@@ -85,12 +88,13 @@ int dev_alloc(spmv_hip_ctx * c, T ** out, size_t n)
 }
 
 int csr_arrays_to_device(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr,
-                         const int32_t * column_index, bool keep_columns, const void * value, bool float_values)
+                         const int32_t * column_index, bool keep_columns, const void * value, bool float_values, bool float_vectors)
 {
     int rc;
     if ((rc = dev_alloc(c, &c->d_ptr, nptr)) != 0 || (keep_columns && (rc = dev_alloc(c, &c->d_col, nnz)) != 0) ||
-        (rc = float_values ? dev_alloc(c, &c->d_val32, nnz) : dev_alloc(c, &c->d_val, nnz)) != 0 || (rc = dev_alloc(c, &c->d_x, nx)) != 0 ||
-        (rc = dev_alloc(c, &c->d_y, ny)) != 0)
+        (rc = float_values ? dev_alloc(c, &c->d_val32, nnz) : dev_alloc(c, &c->d_val, nnz)) != 0 ||
+        (rc = float_vectors ? dev_alloc(c, &c->d_x32, nx) : dev_alloc(c, &c->d_x, nx)) != 0 ||
+        (rc = float_vectors ? dev_alloc(c, &c->d_y32, ny) : dev_alloc(c, &c->d_y, ny)) != 0)
         return rc;
     hipError_t e = hipMemcpyAsync(c->d_ptr, row_ptr, nptr * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nnz > 0 && keep_columns)
@@ -99,9 +103,9 @@ int csr_arrays_to_device(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, si
         e = float_values ? hipMemcpyAsync(c->d_val32, value, nnz * sizeof(float), hipMemcpyHostToDevice, c->stream)
                          : hipMemcpyAsync(c->d_val, value, nnz * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_x, 0, nx * sizeof(double), c->stream);
+        e = float_vectors ? hipMemsetAsync(c->d_x32, 0, nx * sizeof(float), c->stream) : hipMemsetAsync(c->d_x, 0, nx * sizeof(double), c->stream);
     if (e == hipSuccess)
-        e = hipMemsetAsync(c->d_y, 0, ny * sizeof(double), c->stream);
+        e = float_vectors ? hipMemsetAsync(c->d_y32, 0, ny * sizeof(float), c->stream) : hipMemsetAsync(c->d_y, 0, ny * sizeof(double), c->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(c->stream);
     return e == hipSuccess ? SPMV_HIP_OK : fail_hip(e, "upload (host arrays -> device)");
@@ -112,9 +116,9 @@ int csr_arrays_to_device(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, si
 namespace spmvi {
 
 int upload_ctx_csr(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr, const int32_t * column_index,
-                   bool keep_columns, const void * value, bool float_values)
+                   bool keep_columns, const void * value, bool float_values, bool float_vectors)
 {
-    const int rc = csr_arrays_to_device(c, nptr, nx, ny, nnz, row_ptr, column_index, keep_columns, value, float_values);
+    const int rc = csr_arrays_to_device(c, nptr, nx, ny, nnz, row_ptr, column_index, keep_columns, value, float_values, float_vectors);
     if (rc != 0) {
         std::string const why = last_error_text();
         free_ctx_matrix(c);
@@ -733,6 +737,8 @@ int spmv_hip_set_x(spmv_hip_ctx * c, const double * x)
         return fail(SPMV_HIP_ERR_INVALID, "ctx/x null");
     if (c->format == 0)
         return fail(SPMV_HIP_ERR_STATE, "no matrix uploaded");
+    if (c->format == 10)
+        return fail(SPMV_HIP_ERR_STATE, "the context's vectors are floats (spmv_hip_upload_csr_compact_f32xy): use spmv_hip_set_x_f32");
     if (c->multi)
         return multi_set_x(c, x);
     HIP_TRY(hipSetDevice(c->device));
@@ -748,6 +754,8 @@ int spmv_hip_set_y(spmv_hip_ctx * c, const double * y)
         return fail(SPMV_HIP_ERR_INVALID, "ctx/y null");
     if (c->format == 0)
         return fail(SPMV_HIP_ERR_STATE, "no matrix uploaded");
+    if (c->format == 10)
+        return fail(SPMV_HIP_ERR_STATE, "the context's vectors are floats (spmv_hip_upload_csr_compact_f32xy): use spmv_hip_set_y_f32");
     if (c->multi)
         return multi_set_y(c, y);
     HIP_TRY(hipSetDevice(c->device));
@@ -763,11 +771,57 @@ int spmv_hip_get_y(spmv_hip_ctx * c, double * y)
         return fail(SPMV_HIP_ERR_INVALID, "ctx/y null");
     if (c->format == 0)
         return fail(SPMV_HIP_ERR_STATE, "no matrix uploaded");
+    if (c->format == 10)
+        return fail(SPMV_HIP_ERR_STATE, "the context's vectors are floats (spmv_hip_upload_csr_compact_f32xy): use spmv_hip_get_y_f32");
     if (c->multi)
         return multi_get_y(c, y);
     HIP_TRY(hipSetDevice(c->device));
     if (c->rows > 0)
         HIP_TRY(hipMemcpyAsync(y, c->d_y, (size_t) c->rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPMV_HIP_OK;
+}
+
+// the float vectors of a format-10 context (spmv_hip_compact_f32xy.h)
+static int f32_vector_ctx(spmv_hip_ctx * c, const void * v)
+{
+    if (!c || !v)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx/vector null");
+    if (c->format != 10)
+        return fail(SPMV_HIP_ERR_STATE, "float vectors belong to a context of spmv_hip_upload_csr_compact_f32xy");
+    HIP_TRY(hipSetDevice(c->device));
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_set_x_f32(spmv_hip_ctx * c, const float * x)
+{
+    const int rc = f32_vector_ctx(c, x);
+    if (rc != 0)
+        return rc;
+    if (c->cols > 0)
+        HIP_TRY(hipMemcpyAsync(c->d_x32, x, (size_t) c->cols * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_set_y_f32(spmv_hip_ctx * c, const float * y)
+{
+    const int rc = f32_vector_ctx(c, y);
+    if (rc != 0)
+        return rc;
+    if (c->rows > 0)
+        HIP_TRY(hipMemcpyAsync(c->d_y32, y, (size_t) c->rows * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_get_y_f32(spmv_hip_ctx * c, float * y)
+{
+    const int rc = f32_vector_ctx(c, y);
+    if (rc != 0)
+        return rc;
+    if (c->rows > 0)
+        HIP_TRY(hipMemcpyAsync(y, c->d_y32, (size_t) c->rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SPMV_HIP_OK;
 }
@@ -804,6 +858,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
     case 7: rc = spmv_hip_csr_spmv_f32(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
     case 8: rc = spmv_hip_csr_spmv_c16(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
     case 9: rc = spmv_hip_csr_spmv_c16_f64(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
+    case 10: rc = spmv_hip_csr_spmv_c16_f32xy(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, c->d_y32, c->stream); break;
     case 2:
         rc = c->as_csr ? csr_run() : ctx_coo_run(c, c->nnz, c->d_idx, c->d_col, c->d_val);
         break;
@@ -953,11 +1008,11 @@ int spmv_hip_ctx_info(spmv_hip_ctx * c, int64_t * out, int n)
         v[6] = fi[11];
         v[15] = fi[8];
     }
-    if (c->c16_plan) { // formats 8 and 9: workgroups and streamed bytes of the compact plan (format 9: with 8-byte values)
+    if (c->c16_plan) { // formats 8, 9 and 10: workgroups and streamed bytes of the compact plan (9: with 8-byte values; 10: 4-byte vectors)
         int64_t ci[SPMV_HIP_C16_INFO] = {0};
         spmv_hip_c16_plan_info(c->c16_plan, ci, SPMV_HIP_C16_INFO);
         v[6] = ci[4];
-        v[15] = ci[19] + (c->format == 9 && ci[19] ? 4 * ci[2] : 0);
+        v[15] = ci[19] + (c->format == 9 && ci[19] ? 4 * ci[2] : 0) - (c->format == 10 && ci[19] ? 8 * ci[0] + 4 * ci[1] : 0);
     }
     if (c->d_prow)
         v[14] += c->coo_panel_blocks; // COO (part) in column panels: workgroups per panel

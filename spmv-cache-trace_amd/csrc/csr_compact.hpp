@@ -9,6 +9,10 @@
 //
 // csr_compact_f64_kernel is y += A x: the same tile over the caller's fp64 values (ValueQuad<double>: a quad is two
 // 16-byte loads, so per lane four value loads and two code loads go out before anything waits; nothing is widened).
+//
+// csr_compact_f32xy_kernel is y <- fl32(y + fl32(A) x) on FLOAT x and y (include/spmv_hip_compact_f32xy.h): the same tile with
+// the vector element type T = float.  A gather is a 4-byte load widened to fp64, the one-window base goes onto a const float *,
+// and a row's sum is rounded once where it is stored; the products and the LDS slice are doubles as everywhere.
 #pragma once
 
 #include "csr_f32values.hpp"
@@ -57,8 +61,8 @@ struct CompactSource {
 
     __device__ __forceinline__ int at(int k) const { return compact ? CodeColumns<false>{cz, tab}.at(k) : wide.at(k); }
 
-    template <int QUADS, bool X32, class V>
-    __device__ __forceinline__ void products(double * prod, const V * __restrict__ at, const double * __restrict__ x, int kb,
+    template <int QUADS, bool X32, class V, class T>
+    __device__ __forceinline__ void products(double * prod, const V * __restrict__ at, const T * __restrict__ x, int kb,
                                              int last, int lane) const
     {
         if (!compact)
@@ -68,19 +72,19 @@ struct CompactSource {
         else
             quad_products<QUADS, X32>(prod, CodeColumns<false>{cz + kb, tab}, at, x, last, lane);
     }
-    template <bool X32, class V>
-    __device__ __forceinline__ double long_row(const V * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
+    template <bool X32, class V, class T>
+    __device__ __forceinline__ double long_row(const V * __restrict__ a, const T * __restrict__ x, int k0, int k1, int lane) const
     {
         return compact ? long_row_sum_f32<X32>(CodeColumns<false>{cz, tab}, a, x, k0, k1, lane) : wide.long_row<X32>(a, x, k0, k1, lane);
     }
 };
 
-// One wave of either kernel below: its tile's window table into the wave's LDS slot, then the tile over V values.
-template <bool X32, class V>
+// One wave of any kernel below: its tile's window table into the wave's LDS slot, then the tile over V values and T vectors.
+template <bool X32, class V, class T>
 __device__ __forceinline__ void compact_wave(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
                                              const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
-                                             const int32_t * __restrict__ j, const V * __restrict__ a, const double * __restrict__ x,
-                                             double * y, int exact_order)
+                                             const int32_t * __restrict__ j, const V * __restrict__ a, const T * __restrict__ x,
+                                             T * y, int exact_order)
 {
     __shared__ __attribute__((aligned(16))) double prod_all[4][kF32Tile + 4];
     __shared__ int tab_all[4][8];
@@ -120,6 +124,16 @@ __global__ __launch_bounds__(256, 8) void csr_compact_f64_kernel(int ntiles, con
                                                                  const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
                                                                  const int32_t * __restrict__ j, const double * __restrict__ a,
                                                                  const double * __restrict__ x, double * y, int exact_order)
+{
+    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
+}
+
+// y <- fl32(y + fl32(A) x): float x and y beside the float values and the codes; X32: cols * 4 < 2^32
+template <bool X32>
+__global__ __launch_bounds__(256, 8) void csr_compact_f32xy_kernel(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
+                                                                   const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
+                                                                   const int32_t * __restrict__ j, const float * __restrict__ a,
+                                                                   const float * __restrict__ x, float * y, int exact_order)
 {
     compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
 }

@@ -15,6 +15,11 @@
 // The tile also has a VALUE TYPE V: float for the two multiplies of fl32(A), double for csr_compact_f64_kernel
 // (y += A x on the caller's fp64 values beside the 16-bit codes, 10 bytes per entry).  Only ValueQuad<V> differs: how the four
 // values of a quad are loaded and that a float is widened before it is multiplied.
+//
+// ... and a VECTOR ELEMENT TYPE T for x and y: double everywhere but in csr_compact_f32xy_kernel (csr_compact.hpp), whose x and
+// y are floats.  Every x[...] and the row's old y are widened where they are read (exact), the products, the LDS slice and the
+// sums stay fp64, and the one store of a row is (T)(y + sum): one rounding per row and call.  No load or store of x or y is
+// wider than one element, so a float vector needs 4-byte alignment only.
 #pragma once
 
 #include "tile_common.hpp"
@@ -59,9 +64,9 @@ struct ValueQuad<double> {
 // tile_products_wide's rules: lanes past the tile's end re-read its last quad; entries in front of the tile that share its
 // first quad are multiplied and never read back.  cols and at count from the tile's first quad.  Every lane works out its
 // columns (the lanes past the tile's end hold its last quad's); only the gathers are predicated.
-template <int QUADS, bool X32, class Columns, class V>
+template <int QUADS, bool X32, class Columns, class V, class T>
 __device__ __forceinline__ void quad_products(double * prod, const Columns cols, const V * __restrict__ at,
-                                              const double * __restrict__ x, int last, int lane)
+                                              const T * __restrict__ x, int last, int lane)
 {
     typename Columns::quad c[QUADS];
     ValueQuad<V> v[QUADS];
@@ -91,21 +96,21 @@ __device__ __forceinline__ void quad_products(double * prod, const Columns cols,
 // long_row_sum (tile_common.hpp) over float values: the 4-aligned interior [ka, kz) in quads, two per lane and step in
 // flight, four accumulators per lane; the up to three entries in front of ka and behind kz by single lanes.  Nothing is read
 // outside [k0, k1).  cols and a count from entry 0.
-template <bool X32, class Columns, class V>
-__device__ __forceinline__ double long_row_sum_f32(const Columns cols, const V * __restrict__ a, const double * __restrict__ x,
+template <bool X32, class Columns, class V, class T>
+__device__ __forceinline__ double long_row_sum_f32(const Columns cols, const V * __restrict__ a, const T * __restrict__ x,
                                                    int k0, int k1, int lane)
 {
     double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
     const int ka = (k0 + 3) & ~3, kz = k1 & ~3;
     if (ka >= kz) {
         for (int k = k0 + lane; k < k1; k += kWave)
-            z0 += (double) a[k] * x[cols.at(k)];
+            z0 += (double) a[k] * (double) x[cols.at(k)];
         return group_sum<kWave>(z0);
     }
     if (lane < ka - k0)
-        z0 += (double) a[k0 + lane] * x[cols.at(k0 + lane)];
+        z0 += (double) a[k0 + lane] * (double) x[cols.at(k0 + lane)];
     if (lane >= 4 && lane - 4 < k1 - kz)
-        z1 += (double) a[kz + lane - 4] * x[cols.at(kz + lane - 4)];
+        z1 += (double) a[kz + lane - 4] * (double) x[cols.at(kz + lane - 4)];
     for (int o = ka + 4 * lane; o < kz; o += 2 * 4 * kWave) {
         const bool two = o + 4 * kWave < kz;
         const int o2 = two ? o + 4 * kWave : o;
@@ -142,14 +147,14 @@ struct WideSource {
     const int32_t * __restrict__ j;
     __device__ __forceinline__ int at(int k) const { return j[k]; }
     // the products of the tile whose first quad starts at entry kb (at = a + kb)
-    template <int QUADS, bool X32, class V>
-    __device__ __forceinline__ void products(double * prod, const V * __restrict__ at, const double * __restrict__ x, int kb,
+    template <int QUADS, bool X32, class V, class T>
+    __device__ __forceinline__ void products(double * prod, const V * __restrict__ at, const T * __restrict__ x, int kb,
                                              int last, int lane) const
     {
         quad_products<QUADS, X32>(prod, WideColumns{j + kb}, at, x, last, lane);
     }
-    template <bool X32, class V>
-    __device__ __forceinline__ double long_row(const V * __restrict__ a, const double * __restrict__ x, int k0, int k1, int lane) const
+    template <bool X32, class V, class T>
+    __device__ __forceinline__ double long_row(const V * __restrict__ a, const T * __restrict__ x, int k0, int k1, int lane) const
     {
         return long_row_sum_f32<X32>(WideColumns{j}, a, x, k0, k1, lane);
     }
@@ -175,9 +180,9 @@ __device__ __forceinline__ F32Tile load_f32_tile(const int4 * __restrict__ desc,
 }
 
 // One tile by one wave; prod is the wave's LDS slice (kF32Tile + 4 doubles), src the kernel's column source.
-template <bool X32, class Source, class V>
+template <bool X32, class Source, class V, class T>
 __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const Source src, const int32_t * __restrict__ p,
-                                         const V * __restrict__ a, const double * __restrict__ x, double * y, int exact_order)
+                                         const V * __restrict__ a, const T * __restrict__ x, T * y, int exact_order)
 {
     constexpr int TILE = kF32Tile, QUADS = TILE / 256;
     const int lane = (int) __lane_id();
@@ -201,7 +206,7 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             ps = pt[rowi];
             pe = pt[rowi + 1];
         }
-        const double yv = y[r0 + rowi];
+        const double yv = (double) y[r0 + rowi];
         const int last = (k1 - 1 - kb) & ~3;
         src.template products<QUADS, X32>(prod, a + kb, x, kb, last, lane);
         wave_lds_fence();
@@ -221,32 +226,32 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             }
         }
         if (sub < nrows && part == 0)
-            y[r0 + sub] = yv + z;
+            y[r0 + sub] = (T) (yv + z);
     } else if (k1 - kb <= TILE) {
         // ---- a tile of empty rows, or the tile whose last quad is not whole (the ragged end of the arrays): entry by entry,
         // one lane per row, left to right
         for (int k = k0 + lane; k < k1; k += kWave)
-            prod[k - kb] = (double) a[k] * x[src.at(k)];
+            prod[k - kb] = (double) a[k] * (double) x[src.at(k)];
         wave_lds_fence();
         for (int r = lane; r < nrows; r += kWave) {
             const int s = p[r0 + r] - kb, e_row = p[r0 + r + 1] - kb;
             double z = 0.0;
             for (int k = s; k < e_row; ++k)
                 z += prod[k];
-            y[r0 + r] = y[r0 + r] + z;
+            y[r0 + r] = (T) ((double) y[r0 + r] + z);
         }
     } else if (!exact_order) {
         // ---- one row longer than a tile: the whole wave, in registers ----
         const double z = src.template long_row<X32>(a, x, k0, k1, lane);
         if (lane == 0)
-            y[r0] = y[r0] + z;
+            y[r0] = (T) ((double) y[r0] + z);
     } else {
         // ---- ... in the reference's order: lane 0 adds tiles of products left to right ----
         double z = 0.0;
         for (int t0 = k0; t0 < k1; t0 += TILE) {
             const int t1 = (t0 + TILE < k1) ? t0 + TILE : k1;
             for (int k = t0 + lane; k < t1; k += kWave)
-                prod[k - t0] = (double) a[k] * x[src.at(k)];
+                prod[k - t0] = (double) a[k] * (double) x[src.at(k)];
             wave_lds_fence();
             if (lane == 0)
                 for (int k = 0; k < t1 - t0; ++k)
@@ -254,7 +259,7 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             wave_lds_fence();
         }
         if (lane == 0)
-            y[r0] = y[r0] + z;
+            y[r0] = (T) ((double) y[r0] + z);
     }
 }
 

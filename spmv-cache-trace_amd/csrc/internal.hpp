@@ -23,6 +23,7 @@
 #include "spmv_hip_f32values.h"
 #include "spmv_hip_compact.h"
 #include "spmv_hip_compact_f64.h"
+#include "spmv_hip_compact_f32xy.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -217,6 +218,7 @@ struct spmv_hip_ctx {
                     // 7 csr with the values as 4-byte floats (d_val32; no fp64 values are kept),
                     // 8 ... and 16-bit column codes in the plan (d_col only where the plan has wide tiles)
                     // 9 csr with the fp64 values as they are (d_val) and 16-bit column codes in the plan (d_col as for 8)
+                    // 10 format 8 with x and y as 4-byte floats (d_x32 / d_y32; d_x and d_y are null: spmv_hip_compact_f32xy.h)
     int32_t rows = 0, cols = 0, nnz = 0, row_length = 0, nnz2 = 0;
     int csr_algorithm = SPMV_HIP_CSR_AUTO;
     int csr_lanes = 0;
@@ -225,7 +227,8 @@ struct spmv_hip_ctx {
     spmv_hip_tr_plan * tr_plan = nullptr;   // format 6 (transpose.hip)
     spmv_hip_f32_plan * f32_plan = nullptr; // format 7 (f32values.hip)
     float * d_val32 = nullptr;              // ... its values
-    spmv_hip_c16_plan * c16_plan = nullptr; // formats 8 (compact.hip; its values are d_val32 too) and 9 (... d_val)
+    spmv_hip_c16_plan * c16_plan = nullptr; // formats 8 and 10 (compact.hip; their values are d_val32 too) and 9 (... d_val)
+    float *d_x32 = nullptr, *d_y32 = nullptr; // format 10: the vectors
     // block vectors of spmv_hip_run_block (multivec.hip; format 1 only): X (cols x block_k) and Y (rows x block_k), row-major,
     // apart from d_x / d_y; the plan is made on the first run_block after the matrix or k changed
     spmv_hip_mv_plan * mv_plan = nullptr;
@@ -300,10 +303,11 @@ void drop_stencil_runs(spmv_hip_plan * pl);
 // context.hip
 void free_ctx_matrix(spmv_hip_ctx * c);
 // The device side of a Level-1 CSR upload into a context whose matrix was freed: row_ptr (nptr entries), the columns (unless
-// !keep_columns: no d_col), the nnz values (doubles into d_val or, with float_values, floats into d_val32) and zeroed x (nx) and y (ny), every array
+// !keep_columns: no d_col), the nnz values (doubles into d_val or, with float_values, floats into d_val32) and zeroed x (nx) and y (ny; doubles in d_x / d_y
+// or, with float_vectors, floats in d_x32 / d_y32), every array
 // padded by 64 bytes and counted in c->bytes; synchronises.  On failure the matrix is freed and the first error text kept.
 int upload_ctx_csr(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr, const int32_t * column_index,
-                   bool keep_columns, const void * value, bool float_values);
+                   bool keep_columns, const void * value, bool float_values, bool float_vectors = false);
 
 // multi_gpu.hip
 void multi_free_matrix(spmv_hip_ctx * c);

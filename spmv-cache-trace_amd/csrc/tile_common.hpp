@@ -156,13 +156,15 @@ __device__ __forceinline__ T stream_load(const T * ptr)
 }
 
 // x[c] with a 32-bit byte offset from a scalar base when x is smaller than 4 GiB
-// (global_load saddr + voffset: one shift instead of 64-bit address arithmetic)
-template <bool X32>
-__device__ __forceinline__ double gather_x(const double * __restrict__ x, int c)
+// (global_load saddr + voffset: one shift instead of 64-bit address arithmetic).  T = float (csr_compact_f32xy_kernel): the
+// shift is 2, the load 4 bytes wide and the element widened (v_cvt_f64_f32: exact).
+template <bool X32, class T>
+__device__ __forceinline__ double gather_x(const T * __restrict__ x, int c)
 {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4, "x is double or float");
     if (X32)
-        return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(x) + ((unsigned) c << 3));
-    return x[c];
+        return (double) *reinterpret_cast<const T *>(reinterpret_cast<const char *>(x) + ((unsigned) c << (sizeof(T) == 8 ? 3 : 2)));
+    return (double) x[c];
 }
 
 // Sum of one row's products from the wave's LDS slice by L lanes; the trip count is wave-uniform

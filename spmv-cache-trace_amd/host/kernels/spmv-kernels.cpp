@@ -11,6 +11,7 @@
 #include "spmv_hip_f32values.h"
 #include "spmv_hip_compact.h"
 #include "spmv_hip_compact_f64.h"
+#include "spmv_hip_compact_f32xy.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -592,7 +593,9 @@ private:
 };
 
 // --compact: --f32-values with the columns of a tile as 16-bit window codes in the plan; tiles that need more than eight windows
-// multiply from their 32-bit columns, which stay on the device only where there are such tiles
+// multiply from their 32-bit columns, which stay on the device only where there are such tiles.
+// --compact=f32 (options.compact == 4): the same with x and y as 4-byte floats on the device (spmv_hip_compact_f32xy.h): x is
+// narrowed by static_cast<float> on its way there, every run rounds a row's fp64 sum once, and result() widens y
 class hip_csr_compact_spmv_kernel : public hip_kernel_base
 {
 public:
@@ -616,8 +619,12 @@ public:
         if (options.num_gpus == 1)
             options.num_gpus = 0; // --gpus 1: the one-device context this upload needs
         create_context();
-        check(spmv_hip_upload_csr_compact(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(), A.column_index.data(),
-                                          A.value.data(), options.compact == 2 ? 0 : 1), "upload_csr_compact");
+        if (f32xy())
+            check(spmv_hip_upload_csr_compact_f32xy(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(),
+                                                    A.column_index.data(), A.value.data(), 1), "upload_csr_compact_f32xy");
+        else
+            check(spmv_hip_upload_csr_compact(ctx, A.rows, A.columns, A.row_ptr[(std::size_t) A.rows], A.row_ptr.data(), A.column_index.data(),
+                                              A.value.data(), options.compact == 2 ? 0 : 1), "upload_csr_compact");
         std::int64_t info[SPMV_HIP_C16_INFO] = {0};
         check(spmv_hip_c16_plan_preview(A.rows, A.columns, A.row_ptr.data(), A.column_index.data(),
                                         options.hip_flags & SPMV_HIP_FLAG_EXACT_ORDER, info, SPMV_HIP_C16_INFO, nullptr, 0, nullptr),
@@ -625,15 +632,48 @@ public:
         compact_tiles = info[6];
         wide_tiles = info[7];
         compact_entries = info[9];
-        streamed = info[19];
+        streamed = f32xy() && info[19] ? info[19] - 8 * info[0] - 4 * info[1] : info[19];
         init_load_seconds = std::chrono::duration<double>(t1 - t0).count();
         init_upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
     }
-    std::string name() const override { return "hip-csr-spmv-compact"; }
+    void prepare(TraceConfig const & trace_config) override
+    {
+        if (!f32xy())
+            return hip_kernel_base::prepare(trace_config);
+        if (is_master()) {
+            prepare_error.clear();
+            try {
+                std::vector<float> x32(x.size()), y32(y.size());
+                for (std::size_t i = 0; i < x.size(); ++i)
+                    x32[i] = static_cast<float>(x[i]);
+                for (std::size_t i = 0; i < y.size(); ++i)
+                    y32[i] = static_cast<float>(y[i]);
+                if (!x32.empty())
+                    check(spmv_hip_set_x_f32(ctx, x32.data()), "set_x_f32");
+                if (!y32.empty())
+                    check(spmv_hip_set_y_f32(ctx, y32.data()), "set_y_f32");
+            } catch (kernel_error const & e) {
+                prepare_error = e.what();
+            }
+        }
+#pragma omp barrier
+        if (!prepare_error.empty())
+            throw kernel_error(prepare_error);
+    }
+    std::vector<double> result() const override
+    {
+        if (!f32xy())
+            return hip_kernel_base::result();
+        std::vector<float> y32(y.size());
+        if (!y32.empty())
+            check(spmv_hip_get_y_f32(ctx, y32.data()), "get_y_f32");
+        return std::vector<double>(y32.begin(), y32.end());
+    }
+    std::string name() const override { return f32xy() ? "hip-csr-spmv-compact-f32" : "hip-csr-spmv-compact"; }
     std::ostream & print(std::ostream & o) const override
     {
         print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
-        o << ",\n\"value_bytes\": 4,\n\"values_inexact\": " << inexact << ",\n\"max_value_rounding\": " << max_rounding
+        o << ",\n\"value_bytes\": 4" << (f32xy() ? ",\n\"vector_bytes\": 4" : "") << ",\n\"values_inexact\": " << inexact << ",\n\"max_value_rounding\": " << max_rounding
           << ",\n\"compact_tiles\": " << compact_tiles << ",\n\"wide_tiles\": " << wide_tiles << ",\n\"streamed_bytes\": " << streamed;
         return print_device(o) << "\n}";
     }
@@ -642,10 +682,12 @@ public:
     double bytes_per_run() const override
     {
         double const nnz = A.row_ptr[(std::size_t) A.rows];
-        return 6.0 * compact_entries + 8.0 * (nnz - compact_entries) + 4.0 * (A.rows + 1.0) + 16.0 * A.rows + 8.0 * A.columns;
+        double const vector_bytes = f32xy() ? 4.0 : 8.0;
+        return 6.0 * compact_entries + 8.0 * (nnz - compact_entries) + 4.0 * (A.rows + 1.0) + vector_bytes * (2.0 * A.rows + A.columns);
     }
 
 private:
+    bool f32xy() const { return options.compact == 4; }
     csr_matrix::Matrix A;
     long long inexact = 0, compact_tiles = 0, wide_tiles = 0, compact_entries = 0, streamed = 0;
     double max_rounding = 0.0;

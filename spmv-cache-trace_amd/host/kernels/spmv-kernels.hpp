@@ -12,6 +12,7 @@
 //       y += fl32(A) x: the values stored and streamed as 4-byte floats, products and sums in fp64 (hip-csr-spmv-f32values).
 //   hip_csr_compact_spmv_kernel (--compact)
 //       ... with the columns of a tile as 16-bit window codes, 6 bytes per stored entry (hip-csr-spmv-compact).
+//       --compact=f32: ... and x and y as 4-byte floats, every row's fp64 sum rounded once per run (hip-csr-spmv-compact-f32).
 //   hip_csr_compact_f64_spmv_kernel (--compact=f64)
 //       the fp64 values as they are beside the 16-bit window codes, 10 bytes per stored entry (hip-csr-spmv-compact-f64).
 //   hip_csr_transposed_spmv_kernel (--transpose)
@@ -54,6 +55,7 @@ struct SpmvOptions
     int compact = 0;               // EXTENSION: --f32-values (1 = round, 2 = exact) with the columns of a tile as 16-bit window codes
                                    // (--compact[=round|exact]): hip-csr, one device (spmv_hip_upload_csr_compact, spmv_hip_compact.h)
                                    // 3 = f64 (--compact=f64): the fp64 values as they are beside the codes (spmv_hip_upload_csr_compact_f64)
+                                   // 4 = f32 (--compact=f32): 1 with x and y as floats on the device (spmv_hip_upload_csr_compact_f32xy)
     bool round_values_on_host = false; // the CPU CSR kernel multiplies the values rounded by static_cast<float>: what --check
                                    // compares --f32-values with (set by the program, not by an option)
     bool transpose_on_host = false; // the CPU CSR kernel multiplies the matrix transposed on the host: what --check compares

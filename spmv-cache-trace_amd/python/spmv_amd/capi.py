@@ -1,5 +1,6 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
-spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h and spmv_hip_compact_f64.h (the C ABI of libspmv_hip.so).
+spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h and spmv_hip_compact_f32xy.h (the C ABI of
+libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -24,7 +25,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
-                                          "spmv_hip_compact_f64.h")]
+                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -147,6 +148,11 @@ SIGNATURES = {
     "spmv_hip_c16_plan_destroy": (None, [_vp]),
     "spmv_hip_upload_csr_compact": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
     "spmv_hip_upload_csr_compact_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "spmv_hip_csr_spmv_c16_f32xy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_upload_csr_compact_f32xy": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
+    "spmv_hip_set_x_f32": (C.c_int, [_vp, _vp]),
+    "spmv_hip_set_y_f32": (C.c_int, [_vp, _vp]),
+    "spmv_hip_get_y_f32": (C.c_int, [_vp, _vp]),
 }
 
 
@@ -226,6 +232,7 @@ def _f64(a):
 
 _EMPTY_I32 = np.zeros(1, dtype=np.int32)
 _EMPTY_F64 = np.zeros(1, dtype=np.float64)
+_EMPTY_F32 = np.zeros(1, dtype=np.float32)
 
 
 class Context:
@@ -356,6 +363,34 @@ class Context:
             col, val = _EMPTY_I32, _EMPTY_F64
         check(self.lib.spmv_hip_upload_csr_compact_f64(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data))
         self.rows, self.cols = rows, cols
+
+    def upload_csr_compact_f32xy(self, rows, cols, row_ptr, col, val, allow_rounding=True):
+        """upload_csr_compact with x and y as 4-byte floats on the device as well: every run is y <- fl32(y + fl32(A) x), the
+        products and sums in fp64 and one rounding per row; the vectors go through set_x_f32 / set_y_f32 / get_y_f32
+        (include/spmv_hip_compact_f32xy.h)."""
+        row_ptr, col, val = _i32(row_ptr), _i32(col), _f64(val)
+        nnz = int(row_ptr[rows]) if len(row_ptr) > rows >= 0 else -1
+        if len(col) == 0:
+            col, val = _EMPTY_I32, _EMPTY_F64
+        check(self.lib.spmv_hip_upload_csr_compact_f32xy(self.h, rows, cols, nnz, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data,
+                                                         1 if allow_rounding else 0))
+        self.rows, self.cols = rows, cols
+
+    def set_x_f32(self, x):
+        """The float x of a context of upload_csr_compact_f32xy (numpy float32; any other context: ERR_STATE)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert len(x) == self.cols
+        check(self.lib.spmv_hip_set_x_f32(self.h, (x if len(x) else _EMPTY_F32).ctypes.data))
+
+    def set_y_f32(self, y):
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        assert len(y) == self.rows
+        check(self.lib.spmv_hip_set_y_f32(self.h, (y if len(y) else _EMPTY_F32).ctypes.data))
+
+    def get_y_f32(self):
+        y = np.zeros(max(1, self.rows), dtype=np.float32)
+        check(self.lib.spmv_hip_get_y_f32(self.h, y.ctypes.data))
+        return y[:self.rows]
 
     def set_x(self, x):
         x = _f64(x)
@@ -775,6 +810,10 @@ class C16Plan:
     def spmv_f64(self, d_row_ptr, d_col, d_val, d_x, d_y, stream=0):
         """y += A x through the same plan; d_val an fp64 array (16-byte aligned), otherwise as spmv."""
         check(self.lib.spmv_hip_csr_spmv_c16_f64(self.h, d_row_ptr, d_col or None, d_val, d_x, d_y, stream))
+
+    def spmv_f32xy(self, d_row_ptr, d_col, d_val32, d_x32, d_y32, stream=0):
+        """y <- fl32(y + fl32(A) x) through the same plan; d_x32 and d_y32 float arrays (4-byte aligned), otherwise as spmv."""
+        check(self.lib.spmv_hip_csr_spmv_c16_f32xy(self.h, d_row_ptr, d_col or None, d_val32, d_x32, d_y32, stream))
 
     def verify(self, d_col, stream=0):
         """How many entries of compact tiles decode to a column other than d_col's (the content guard)."""

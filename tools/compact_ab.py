@@ -6,13 +6,15 @@ each), torch tensors, interleaved rounds after a warm-up, each round the median 
     c16     spmv_hip_csr_spmv_c16
     f32     spmv_hip_csr_spmv_f32 over the same float values and 32-bit columns
     c16_f64 spmv_hip_csr_spmv_c16_f64 (include/spmv_hip_compact_f64.h): the c16 plan object over the fp64 values, 10 bytes per entry
+    c16_f32xy spmv_hip_csr_spmv_c16_f32xy (include/spmv_hip_compact_f32xy.h): the c16 plan object and float values over float32 x and y
     fp64    spmv_hip_csr_spmv with the plan spmv_hip_upload_csr builds (tiles, block confirmation, compression, panels, dictionary)
 
 Per matrix: microseconds per multiply (median and min over the rounds), the ratios, the three plans' streamed bytes from their
 plan_info, each launch's streamed bytes / time as a share of the STREAM triad timed in the same process, the share of the
 stored entries in compact tiles, the windows histogram, the host planning time in ms and whether c16 and f32 gave the same
 bits (and c16_f64 the bits of fp64 is NOT expected: the default plan adds a row in another order).  The log goes to stdout and
-to profiles/compact_ab.log (--log: the run that added c16_f64 went to profiles/compact_f64_ab.log).
+to profiles/compact_ab.log (--log: the run that added c16_f64 went to profiles/compact_f64_ab.log, the one that added c16_f32xy
+to profiles/compact_f32xy_ab.log).
 
     python tools/compact_ab.py
     python tools/compact_ab.py --only delaunay_1dof mesh_128 --rounds 25
@@ -114,10 +116,14 @@ def measure(name, spec, rounds, reps):
     same_bits = bool(torch.equal(ya.view(torch.int64), yb.view(torch.int64)))
     del ya, yb
 
+    # float32 x and y of c16_f32xy: x narrowed once, a y of its own (y is the doubles' y: the other ways get its address)
+    tx32 = tx.to(torch.float32)
+    y32 = torch.zeros(rows, dtype=torch.float32, device=dev)
     ways = {
         "c16": lambda y: c16.spmv(tp.data_ptr(), tc.data_ptr(), tf.data_ptr(), tx.data_ptr(), y, stream),
         "f32": lambda y: f32.spmv(tp.data_ptr(), tc.data_ptr(), tf.data_ptr(), tx.data_ptr(), y, stream),
         "c16_f64": lambda y: c16.spmv_f64(tp.data_ptr(), tc.data_ptr(), tv.data_ptr(), tx.data_ptr(), y, stream),
+        "c16_f32xy": lambda y: c16.spmv_f32xy(tp.data_ptr(), tc.data_ptr(), tf.data_ptr(), tx32.data_ptr(), y32.data_ptr(), stream),
         "fp64": lambda y: plan.spmv(tp.data_ptr(), tc.data_ptr(), tv.data_ptr(), tx.data_ptr(), y, stream),
     }
     y = torch.zeros(rows, dtype=torch.float64, device=dev)
@@ -137,7 +143,8 @@ def measure(name, spec, rounds, reps):
     ci, fi, di = c16.info(), f32.info(), plan.info()
     med = {k: float(np.median(t)) for k, t in times.items()}
     sb = {"c16": ci["streamed_bytes"], "f32": fi["streamed_bytes"], "fp64": di["streamed_bytes"],
-          "c16_f64": ci["streamed_bytes"] + 4 * nnz if ci["streamed_bytes"] else 0}
+          "c16_f64": ci["streamed_bytes"] + 4 * nnz if ci["streamed_bytes"] else 0,
+          "c16_f32xy": ci["streamed_bytes"] - 8 * rows - 4 * cols if ci["streamed_bytes"] else 0}
     res = {
         "matrix": name, "spec": spec, "rows": rows, "cols": cols, "stored_entries": nnz, "load_s": round(load_s, 1),
         "library": os.path.basename(capi.LIB_PATH),
@@ -145,6 +152,7 @@ def measure(name, spec, rounds, reps):
         "us": {k: {"median": round(med[k], 2), "min": round(float(np.min(t)), 2)} for k, t in times.items()},
         "ratio_c16_over_f32": round(med["c16"] / med["f32"], 3), "ratio_c16_over_fp64": round(med["c16"] / med["fp64"], 3),
         "ratio_c16_f64_over_fp64": round(med["c16_f64"] / med["fp64"], 3), "byte_ratio_c16_f64_over_fp64": round(sb["c16_f64"] / max(1, sb["fp64"]), 3),
+        "ratio_c16_f32xy_over_c16": round(med["c16_f32xy"] / med["c16"], 3), "byte_ratio_c16_f32xy_over_c16": round(sb["c16_f32xy"] / max(1, sb["c16"]), 3),
         "streamed_bytes": {k: sb[k] for k in ways},
         "byte_ratio_c16_over_f32": round(sb["c16"] / max(1, sb["f32"]), 3), "byte_ratio_c16_over_fp64": round(sb["c16"] / max(1, sb["fp64"]), 3),
         "share_of_triad": {k: round(sb[k] / (med[k] * 1e-6) / 1e9 / triad, 3) for k in ways},
@@ -179,7 +187,7 @@ def main():
         log.flush()
 
     say("c16 = spmv_hip_csr_spmv_c16 (float values, 16-bit column codes); f32 = spmv_hip_csr_spmv_f32; c16_f64 = spmv_hip_csr_spmv_c16_f64 "
-        "(fp64 values, the same codes); fp64 = spmv_hip_csr_spmv with the default plan; one process per matrix (rounds %d, each the median of %d launches)" % (args.rounds, args.reps))
+        "(fp64 values, the same codes); c16_f32xy = spmv_hip_csr_spmv_c16_f32xy (c16 over float32 x and y); fp64 = spmv_hip_csr_spmv with the default plan; one process per matrix (rounds %d, each the median of %d launches)" % (args.rounds, args.reps))
     for name, spec, what in MATRICES:
         if args.only and name not in args.only:
             continue
@@ -197,8 +205,9 @@ def main():
         say("%-14s %s: %d x %d, %d stored entries; triad %.0f GB/s; %s" % (
             name, what, res["rows"], res["cols"], res["stored_entries"], res["triad_gbs"], res["library"]))
         for k in us:
-            say("    %-8s median %9.2f us  min %9.2f us   streams %12d bytes   %.2f of triad" % (k, us[k]["median"], us[k]["min"], sb[k], sh[k]))
+            say("    %-9s median %9.2f us  min %9.2f us   streams %12d bytes   %.2f of triad" % (k, us[k]["median"], us[k]["min"], sb[k], sh[k]))
         say("    c16_f64 / fp64 (median) %.3f, by bytes %.3f" % (res["ratio_c16_f64_over_fp64"], res["byte_ratio_c16_f64_over_fp64"]))
+        say("    c16_f32xy / c16 (median) %.3f, by bytes %.3f" % (res["ratio_c16_f32xy_over_c16"], res["byte_ratio_c16_f32xy_over_c16"]))
         say("    c16 / f32 (median) %.3f, by bytes %.3f;  c16 / fp64 %.3f, by bytes %.3f;  compact tiles hold %.4f of the entries "
             "(%d compact, %d wide; windows 1..8: %r);  planned on the host in %.0f ms;  verify: %d mismatches;  c16 bits == f32 bits: %s" % (
                 res["ratio_c16_over_f32"], res["byte_ratio_c16_over_f32"], res["ratio_c16_over_fp64"], res["byte_ratio_c16_over_fp64"],
