@@ -259,10 +259,8 @@ def test_one_row_one_column_and_empty_shapes():
     _check_both(10, 12, np.zeros(11, np.int32), np.zeros(0, np.int32), np.zeros(0), "no entries")
 
 
-@pytest.mark.parametrize("window_doubles", [0, 100])
-def test_ranges_that_start_and_end_inside_a_quad(window_doubles):
-    """Row lengths 0 .. 7 at random: nnz is not a multiple of 4 and nearly every range boundary (every 2048 rows, or every 100
-    with window_doubles = 100) falls inside an aligned quad of entries."""
+def _quad_matrix():
+    """Row lengths 0 .. 7 at random, nnz no multiple of 4 (test_ranges_that_start_and_end_inside_a_quad)."""
     rng = np.random.default_rng(13)
     rows, cols = 10007, 9001
     lens = rng.integers(0, 8, size=rows)
@@ -274,6 +272,14 @@ def test_ranges_that_start_and_end_inside_a_quad(window_doubles):
     assert nnz % 4 != 0
     c = np.concatenate([np.sort(rng.choice(cols, size=int(p[r + 1] - p[r]), replace=False)) for r in range(rows)]).astype(np.int32)
     v = rng.uniform(-1.0, 1.0, size=nnz)
+    return rows, cols, p, c, v
+
+
+@pytest.mark.parametrize("window_doubles", [0, 100])
+def test_ranges_that_start_and_end_inside_a_quad(window_doubles):
+    """Row lengths 0 .. 7 at random: nnz is not a multiple of 4 and nearly every range boundary (every 2048 rows, or every 100
+    with window_doubles = 100) falls inside an aligned quad of entries."""
+    rows, cols, p, c, v = _quad_matrix()
     R = window_doubles or 2048
     assert np.any(p[R:rows:R] % 4 != 0)
     _check_both(rows, cols, p, c, v, "row lengths 0..7, window_doubles=%d" % window_doubles, window_doubles=window_doubles)
