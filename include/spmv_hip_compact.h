@@ -55,7 +55,9 @@ int spmv_hip_c16_plan_csr(spmv_hip_c16_plan **plan, int32_t rows, int32_t cols, 
  * pointer with wide tiles present is SPMV_HIP_ERR_INVALID.  Where given it must hold the columns the plan was made from
  * (spmv_hip_c16_plan_verify checks that).  d_column_index (where given) and d_value must be 16-byte aligned
  * (SPMV_HIP_ERR_ALIGN); d_x == d_y is SPMV_HIP_ERR_INVALID; rows, cols or nnz of zero is a valid matrix whose multiply does
- * nothing.  Nothing is read beyond the 16 bytes that hold entry nnz - 1 of either caller array. */
+ * nothing.  Nothing is read beyond the 16 bytes that hold entry nnz - 1 of either caller array.
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_spmv_c16(const spmv_hip_c16_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                           const float *d_value, const double *d_x, double *d_y, void *stream);
 /* The content guard: decodes every entry of every compact tile on the device and counts those whose column differs from

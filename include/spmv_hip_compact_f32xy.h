@@ -32,7 +32,9 @@ extern "C" {
 /* The tiles, lanes, products (a multiply, then an add: no FMA) and sums of spmv_hip_csr_spmv_c16 in the order the plan fixes.
  * The refusals are those of spmv_hip_csr_spmv_c16, and d_x and d_y need only be 4-byte aligned (SPMV_HIP_ERR_ALIGN otherwise),
  * so a slice of a larger float tensor can be passed.  Bytes one multiply streams: spmv_hip_c16_plan_info [19] - 8 * [0] - 4 * [1]
- * (y 8 instead of 16 per row, x 4 instead of 8 per column) where the multiply does something, else 0. */
+ * (y 8 instead of 16 per row, x 4 instead of 8 per column) where the multiply does something, else 0.
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_spmv_c16_f32xy(const spmv_hip_c16_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                                 const float *d_value, const float *d_x, float *d_y, void *stream);
 

@@ -27,7 +27,9 @@ extern "C" {
  * and under SPMV_HIP_FLAG_EXACT_ORDER the reference's y on any values.  The refusals are those of spmv_hip_csr_spmv_c16; d_value
  * need only be 16-byte aligned (a quad of four doubles is read as two 16-byte loads).  Nothing is read in front of entry 0 or
  * beyond entry nnz - 1 of d_value.  Bytes one multiply streams: spmv_hip_c16_plan_info [19] + 4 * [2] (10 per stored entry of
- * a compact tile, 12 per stored entry of a wide one) where the multiply does something, else 0. */
+ * a compact tile, 12 per stored entry of a wide one) where the multiply does something, else 0.
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_spmv_c16_f64(const spmv_hip_c16_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                               const double *d_value, const double *d_x, double *d_y, void *stream);
 

@@ -55,7 +55,9 @@ int spmv_hip_f32_plan_csr(spmv_hip_f32_plan **plan, int32_t rows, int32_t cols, 
                           void *stream);
 /* y += fl32(A) x.  Columns must lie in [0, cols) (not checked here: spmv_hip_csr_spmv's rule).  d_column_index and d_value
  * must be 16-byte aligned (SPMV_HIP_ERR_ALIGN); d_x == d_y is SPMV_HIP_ERR_INVALID; rows, cols or nnz of zero is a valid
- * matrix whose multiply does nothing.  Nothing is read beyond the 16 bytes that hold entry nnz - 1 of either array. */
+ * matrix whose multiply does nothing.  Nothing is read beyond the 16 bytes that hold entry nnz - 1 of either array.
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_spmv_f32(const spmv_hip_f32_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                           const float *d_value, const double *d_x, double *d_y, void *stream);
 /* out[]: [0] rows  [1] cols  [2] stored entries  [3] tiles (one wave each)  [4] long-row tiles (one row of more entries than a

@@ -38,7 +38,9 @@ typedef struct spmv_hip_mv_plan spmv_hip_mv_plan;
 int spmv_hip_mv_plan_csr(spmv_hip_mv_plan **plan, int32_t rows, int32_t cols, const int32_t *host_row_ptr, int k,
                          unsigned flags, void *stream);
 /* Y += A X with the plan's k.  d_row_ptr must hold the row_ptr the plan was made from; every column index must lie in
- * [0, cols) (not checked here: spmv_hip_csr_spmv's rule).  d_X == d_Y: SPMV_HIP_ERR_INVALID. */
+ * [0, cols) (not checked here: spmv_hip_csr_spmv's rule).  d_X == d_Y: SPMV_HIP_ERR_INVALID.
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_spmm(const spmv_hip_mv_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                       const double *d_value, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, void *stream);
 /* out[]: [0] rows  [1] cols  [2] k  [3] passes over the matrix  [4] wave tiles  [5] long rows (a workgroup each)

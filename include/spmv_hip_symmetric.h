@@ -60,7 +60,9 @@ typedef struct spmv_hip_sym_plan spmv_hip_sym_plan;
  * plan_info numbers then describe the old one).  The triangle and kind are checked here; keep the matrix a triangle. */
 int spmv_hip_sym_plan_csr(spmv_hip_sym_plan **plan, int32_t rows, const int32_t *host_row_ptr, const int32_t *d_column_index,
                           int kind, int max_windows, int window_doubles, void *stream);
-/* y += (T +- T' [- diag]) x.  d_x and d_y must be different arrays (d_x == d_y: SPMV_HIP_ERR_INVALID). */
+/* y += (T +- T' [- diag]) x.  d_x and d_y must be different arrays (d_x == d_y: SPMV_HIP_ERR_INVALID).
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_symv(const spmv_hip_sym_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                       const double *d_value, const double *d_x, double *d_y, void *stream);
 /* out[]: [0] ranges (workgroups)  [1] rows per range  [2] windows per range at most (own rows' included)

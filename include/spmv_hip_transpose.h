@@ -55,7 +55,9 @@ int spmv_hip_tr_plan_preview(int32_t rows, int32_t cols, const int32_t *host_row
 int spmv_hip_tr_plan_csr(spmv_hip_tr_plan **plan, int32_t rows, int32_t cols, const int32_t *host_row_ptr,
                          const int32_t *d_column_index, int max_windows, int window_doubles, void *stream);
 /* y += A' x: d_x has rows entries, d_y has cols.  d_x and d_y must be different arrays (d_x == d_y: SPMV_HIP_ERR_INVALID);
- * d_column_index and d_value must be 16-byte aligned (SPMV_HIP_ERR_ALIGN). */
+ * d_column_index and d_value must be 16-byte aligned (SPMV_HIP_ERR_ALIGN).
+ * The multiply only enqueues work on `stream`: it neither synchronises nor allocates, and may be captured into a graph
+ * (tests/test_gpu_streams.py). */
 int spmv_hip_csr_spmv_t(const spmv_hip_tr_plan *plan, const int32_t *d_row_ptr, const int32_t *d_column_index,
                         const double *d_value, const double *d_x, double *d_y, void *stream);
 /* out[]: [0] ranges (workgroups)  [1] rows per range  [2] windows per range at most  [3] windows used, summed over the ranges

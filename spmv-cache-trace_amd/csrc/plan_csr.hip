@@ -34,6 +34,17 @@ hipError_t read_striped(const T * d_counters, T * out, int n, hipStream_t s)
     return e;
 }
 
+// Plan time: what a kernel of the step wrote on `s` comes back to the host ON `s`.  A blocking hipMemcpy runs on the null stream,
+// which a non-blocking caller stream does not wait for: it would be ordered behind the producer only by whatever synchronisation
+// of `s` happened to precede it.
+hipError_t read_back(void * host, const void * dev, size_t bytes, hipStream_t s)
+{
+    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    return e;
+}
+
 } // namespace
 
 namespace spmvi {
@@ -168,7 +179,8 @@ void drop_stencil_runs(spmv_hip_plan * pl)
 // multiples of 128 rows (a range edge elsewhere moves a cut by a row rather than leave a chunk of one row); a chunk that holds a
 // row with missing positions gets 128 row masks in a side array.  The other tiles keep their descriptors and go to the rest list.
 // Nothing changes what a multiply streams: plan_account's numbers stay as they are.
-static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, bool compressed)
+// `s`: the stream of the planning step that asks (its kernels wrote the 16-bit column slots and the pattern records).
+static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, bool compressed, hipStream_t s)
 {
     drop_stencil_runs(pl);
     const bool exact_order = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) != 0;
@@ -236,7 +248,7 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
     if (2 * per_pattern[(size_t) P] <= (long long) pl->nnz)
         return SPMV_HIP_OK; // runs pay only where they cover most of the matrix
     std::vector<int32_t> recs((size_t) pl->npatterns * spmv::kPatStride);
-    HIP_TRY(hipMemcpy(recs.data(), pl->d_patterns, recs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(read_back(recs.data(), pl->d_patterns, recs.size() * sizeof(int32_t), s));
     spmv::RunPattern rp{};
     for (int q = 0; q < L; ++q)
         rp.rel[q] = recs[(size_t) P * spmv::kPatStride + spmv::kPatRel + q];
@@ -286,14 +298,15 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
             uint16_t * d_out = nullptr;
             hipError_t e = hipMalloc((void **) &d_idx, idx.size() * sizeof(int32_t));
             if (e == hipSuccess) e = hipMalloc((void **) &d_out, idx.size() * sizeof(uint16_t));
+            // (a blocking copy into a fresh allocation: complete when it returns, whatever stream the gather runs on)
             if (e == hipSuccess) e = hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(run_gather_u16, dim3((unsigned) ((idx.size() + 255) / 256)), dim3(256), 0, 0,
+                hipLaunchKernelGGL(run_gather_u16, dim3((unsigned) ((idx.size() + 255) / 256)), dim3(256), 0, s,
                                    (const uint16_t *) pl->d_col16, d_idx, d_out, (int) idx.size());
                 e = hipGetLastError();
             }
             tmask.resize(idx.size());
-            if (e == hipSuccess) e = hipMemcpy(tmask.data(), d_out, tmask.size() * sizeof(uint16_t), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = read_back(tmask.data(), d_out, tmask.size() * sizeof(uint16_t), s);
             (void) hipFree(d_idx);
             (void) hipFree(d_out);
             HIP_TRY(e);
@@ -450,7 +463,8 @@ static int build_stencil_runs(spmv_hip_plan * pl, const std::vector<int4> & d, b
 // values 8 B per entry; columns 4 B (wide), 2 B (16-bit), one first row (shifted) or nothing
 // (shifted with a pattern); row_ptr 4 B per row of a non-uniform tile; y 16 B per row; x once;
 // 16 B of descriptor per tile.
-int plan_account(spmv_hip_plan * pl, bool compressed)
+// `s`: the stream of the planning step that asks; the descriptors its kernels marked are read back on it.
+int plan_account(spmv_hip_plan * pl, bool compressed, hipStream_t s)
 {
     const long long algorithmic = 12LL * pl->nnz + 4LL * (pl->rows + 1LL) + 16LL * pl->rows + 8LL * pl->cols;
     pl->streamed_bytes = algorithmic;
@@ -462,7 +476,7 @@ int plan_account(spmv_hip_plan * pl, bool compressed)
     const bool vi_tiles = pl->nvalues > 0 && pl->d_tiles_vi;
     const int ntiles = vi_tiles ? pl->ntiles_vi : pl->ntiles;
     std::vector<int4> d((size_t) ntiles + 1);
-    HIP_TRY(hipMemcpy(d.data(), vi_tiles ? pl->d_tiles_vi : pl->d_tiles, d.size() * sizeof(int4), hipMemcpyDeviceToHost));
+    HIP_TRY(read_back(d.data(), vi_tiles ? pl->d_tiles_vi : pl->d_tiles, d.size() * sizeof(int4), s));
     long long bytes = 8LL * pl->cols;
     for (int w = 0; w < ntiles; ++w) {
         const long long entries = (long long) d[(size_t) w + 1].y - d[(size_t) w].y;
@@ -536,7 +550,7 @@ int plan_account(spmv_hip_plan * pl, bool compressed)
             pl->nrest_tiles += !(d[(size_t) w].z & spmv::kTileMetaBlockWin);
     }
     {
-        int rc = build_stencil_runs(pl, d, compressed); // (returns at once under a value dictionary)
+        int rc = build_stencil_runs(pl, d, compressed, s); // (returns at once under a value dictionary)
         if (rc != SPMV_HIP_OK)
             return rc;
     }
@@ -1301,7 +1315,7 @@ int plan_csr_internal(spmv_hip_plan ** out, int32_t rows, int32_t cols, const in
             }
         }
     }
-    int rc_acc = plan_account(pl, false);
+    int rc_acc = plan_account(pl, false, nullptr); // (no stream yet: the descriptors went up with a blocking copy)
     if (rc_acc != SPMV_HIP_OK) {
         spmv_hip_plan_destroy(pl);
         return rc_acc;
@@ -1654,7 +1668,7 @@ int spmv_hip_plan_csr_compress(spmv_hip_plan * pl, const int32_t * d_column_inde
         rc = plan_hub_columns(pl, d_column_index, s);
 #endif
     if (rc == SPMV_HIP_OK)
-        rc = plan_account(pl, true);
+        rc = plan_account(pl, true, s);
     pl->verify_pending = true;
     return rc;
 }
@@ -1752,7 +1766,7 @@ static int rebuild_tiles(spmv_hip_plan * pl, const int32_t * d_row_ptr, const in
     int rc = build_wave_tiles(pl, host_row_ptr, pl->flags, pl->break_rows, kSplitThreshold, kSplitChunk);
     pl->group_bits = nullptr;
     if (rc == SPMV_HIP_OK)
-        rc = plan_account(pl, false);
+        rc = plan_account(pl, false, s);
     if (rc == SPMV_HIP_OK && was_compressed)
         rc = spmv_hip_plan_csr_compress(pl, d_column_index, stream);
     return rc;
@@ -1906,7 +1920,7 @@ static int repack_stages(spmv_hip_plan * pl, const int32_t * d_row_ptr, const in
                 return rc;
             hint_was_wrong = true;
         } else if (pl->block_tiles > 0 || pl->colshare_tiles > 0) {
-            int rc = plan_account(pl, true);
+            int rc = plan_account(pl, true, s);
             if (rc != SPMV_HIP_OK)
                 return rc;
         }
@@ -1957,7 +1971,7 @@ static int repack_stages(spmv_hip_plan * pl, const int32_t * d_row_ptr, const in
         std::vector<int32_t> pat;
         if (pl->npatterns > 0) {
             pat.resize((size_t) pl->npatterns * spmv::kPatStride);
-            HIP_TRY(hipMemcpy(pat.data(), pl->d_patterns, pat.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(read_back(pat.data(), pl->d_patterns, pat.size() * sizeof(int32_t), s));
         }
         spmv::StencilTryList list{0, {0, 0, 0, 0, 0, 0, 0, 0}};
         int np = pl->npatterns;
@@ -2060,7 +2074,7 @@ static int repack_stages(spmv_hip_plan * pl, const int32_t * d_row_ptr, const in
             pl->stencil_mask_tiles = (int) count[0];
             pl->stencil_mask_entries = (long long) count[1];
             if (count[0] > 0) {
-                int rc = plan_account(pl, true);
+                int rc = plan_account(pl, true, s);
                 if (rc != SPMV_HIP_OK)
                     return rc;
             }
@@ -2163,24 +2177,25 @@ static int repack_stages(spmv_hip_plan * pl, const int32_t * d_row_ptr, const in
 // two adjacent rows per lane 128 rows keep all 64 lanes busy (a 5-point tile of 512 entries has 102 rows: 51 lanes).  Every
 // other tile is copied as it is.  Only tiles that refer to a shared pattern are merged (their first-row columns are known to be
 // the same without looking at the column array).
-static hipError_t merge_constant_row_tiles(spmv_hip_plan * pl, const uint8_t * d_same_prev)
+// `s`: the stream value_rows_mark_kernel marked the descriptors and wrote d_same_prev on.
+static hipError_t merge_constant_row_tiles(spmv_hip_plan * pl, const uint8_t * d_same_prev, hipStream_t s)
 {
 #if defined(SPMV_HIP_EXPERIMENTS) && defined(SPMV_VI_ABLATE)
     return hipSuccess; // the ablation builds switch the constant-row path off: every tile has to fit the general path
 #endif
     std::vector<int4> d((size_t) pl->ntiles + 1);
-    hipError_t e = hipMemcpy(d.data(), pl->d_tiles, d.size() * sizeof(int4), hipMemcpyDeviceToHost);
+    hipError_t e = read_back(d.data(), pl->d_tiles, d.size() * sizeof(int4), s);
     if (e != hipSuccess)
         return e;
     // same_prev[w]: tile w's first row carries the dictionary bytes of tile w - 1's (value_rows_mark_kernel, byte by byte)
     std::vector<uint8_t> same_prev((size_t) pl->ntiles, 0);
-    e = hipMemcpy(same_prev.data(), d_same_prev, same_prev.size(), hipMemcpyDeviceToHost);
+    e = read_back(same_prev.data(), d_same_prev, same_prev.size(), s);
     if (e != hipSuccess)
         return e;
     std::vector<int32_t> pat;
     if (pl->d_patterns && pl->npatterns > 0) {
         pat.resize((size_t) pl->npatterns * spmv::kPatStride);
-        e = hipMemcpy(pat.data(), pl->d_patterns, pat.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+        e = read_back(pat.data(), pl->d_patterns, pat.size() * sizeof(int32_t), s);
         if (e != hipSuccess)
             return e;
     }
@@ -2288,7 +2303,7 @@ int spmv_hip_plan_csr_index_values(spmv_hip_plan * pl, const double * d_value, v
         || !pl->d_col16 || other_variant || pl->cols >= (1 << 29)
         || (pl->flags & SPMV_HIP_FLAG_NO_VALUE_INDEX))
         return (pl->inner || before == 0) ? SPMV_HIP_OK // nothing was dropped: the account of plan / compress still holds
-                                          : plan_account(pl, pl->d_col16 != nullptr);
+                                          : plan_account(pl, pl->d_col16 != nullptr, s);
     if (!d_value)
         return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
     unsigned long long * d_keys = nullptr;
@@ -2362,7 +2377,7 @@ int spmv_hip_plan_csr_index_values(spmv_hip_plan * pl, const double * d_value, v
             if (d_count) (void) hipFree(d_count);
             pl->value_row_tiles = (int) count[0];
             if (e == hipSuccess && count[0] > 0)
-                e = merge_constant_row_tiles(pl, d_same_prev);
+                e = merge_constant_row_tiles(pl, d_same_prev, s);
             if (d_same_prev) (void) hipFree(d_same_prev);
         }
         if (e == hipSuccess && state[1] == 0) {
@@ -2387,7 +2402,7 @@ int spmv_hip_plan_csr_index_values(spmv_hip_plan * pl, const double * d_value, v
     }
     if (pl->nvalues == 0 && before == 0)
         return SPMV_HIP_OK; // more than 128 distinct values and nothing dropped: the account is unchanged (no descriptor download)
-    return plan_account(pl, pl->d_col16 != nullptr);
+    return plan_account(pl, pl->d_col16 != nullptr, s);
 }
 
 int spmv_hip_plan_csr_refresh_values(spmv_hip_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
