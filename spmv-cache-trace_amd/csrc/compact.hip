@@ -220,15 +220,24 @@ int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
 }
 
 // spmv_hip_csr_spmv_c16 (V = float, T = double), spmv_hip_csr_spmv_c16_f64 (V = double) and spmv_hip_csr_spmv_c16_f32xy (V = T =
-// float): the plan knows neither the value type nor the vectors' element type
+// float): the plan knows neither the value type nor the vectors' element type.  With a scale (spmv_hip_scaled.h) d_y is y_out
+// and the same refusals apply; without one it is y += A x.
 template <class V, class T>
 int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const V * d_value,
-                 const T * d_x, T * d_y, void * stream)
+                 const T * d_x, T * d_y, void * stream, const ScaledArgs<T> * scale = nullptr)
 {
     if (!pl)
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
     if (d_x && (const void *) d_x == (const void *) d_y)
         return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (scale) {
+        const int rc = scaled_vectors_check(pl->rows, sizeof(T), scale->beta, scale->y_in, d_y);
+        if (rc != 0 || pl->rows == 0)
+            return rc;
+        if (scale->alpha == 0.0 || pl->ntiles == 0) // the beta part alone: neither the matrix nor x is read
+            return scaled_rows_only(pl->rows, std::is_same<T, float>::value, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, s);
+    }
     if (pl->ntiles == 0) // rows, cols or nnz of zero
         return SPMV_HIP_OK;
     if (!d_row_ptr || !d_value || !d_x || !d_y)
@@ -240,10 +249,26 @@ int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const 
     if constexpr (std::is_same<T, float>::value) // (the kernel reads and writes x and y one element at a time)
         if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_y)) & 3u)
             return fail(SPMV_HIP_ERR_ALIGN, "d_x and d_y must be 4-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
     const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
     const bool x32 = (long long) pl->cols * (long long) sizeof(T) < (1LL << 32);
+    if (scale) {
+        const bool beta0 = scale->beta == 0.0;
+        void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, double, double,
+                       const T *, T *, int);
+#define SPMV_C16_PICK(NAME) (x32 ? (beta0 ? spmv::NAME<true, true> : spmv::NAME<true, false>) : (beta0 ? spmv::NAME<false, true> : spmv::NAME<false, false>))
+        if constexpr (std::is_same<T, float>::value)
+            kernel = SPMV_C16_PICK(csr_compact_f32xy_scaled_kernel);
+        else if constexpr (std::is_same<V, float>::value)
+            kernel = SPMV_C16_PICK(csr_compact_scaled_kernel);
+        else
+            kernel = SPMV_C16_PICK(csr_compact_f64_scaled_kernel);
+#undef SPMV_C16_PICK
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
+                           scale->alpha, scale->beta, scale->y_in, d_y, exact);
+        HIP_TRY(hipGetLastError());
+        return SPMV_HIP_OK;
+    }
     void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, T *, int);
     if constexpr (std::is_same<T, float>::value)
         kernel = x32 ? spmv::csr_compact_f32xy_kernel<true> : spmv::csr_compact_f32xy_kernel<false>;
@@ -372,6 +397,27 @@ int spmv_hip_csr_spmv_c16_f32xy(const spmv_hip_c16_plan * pl, const int32_t * d_
                                 const float * d_x, float * d_y, void * stream)
 {
     return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream);
+}
+
+int spmv_hip_csr_spmv_c16_scaled(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                                 const double * d_x, double alpha, double beta, const double * d_y_in, double * d_y_out, void * stream)
+{
+    const ScaledArgs<double> scale{alpha, beta, d_y_in};
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale);
+}
+
+int spmv_hip_csr_spmv_c16_f64_scaled(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value,
+                                     const double * d_x, double alpha, double beta, const double * d_y_in, double * d_y_out, void * stream)
+{
+    const ScaledArgs<double> scale{alpha, beta, d_y_in};
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale);
+}
+
+int spmv_hip_csr_spmv_c16_f32xy_scaled(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                                       const float * d_x, double alpha, double beta, const float * d_y_in, float * d_y_out, void * stream)
+{
+    const ScaledArgs<float> scale{alpha, beta, d_y_in};
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale);
 }
 
 int spmv_hip_c16_plan_verify(const spmv_hip_c16_plan * pl, const int32_t * d_column_index, int64_t * mismatches, void * stream)

@@ -889,6 +889,38 @@ int spmv_hip_run(spmv_hip_ctx * c)
     return SPMV_HIP_OK;
 }
 
+// spmv_hip_scaled.h: the context's y <- alpha A x + beta y, in place, for the four float-tile formats
+int spmv_hip_run_scaled(spmv_hip_ctx * c, double alpha, double beta)
+{
+    if (!c)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
+    if (c->multi)
+        return fail(SPMV_HIP_ERR_STATE, "spmv_hip_run_scaled runs on one device (a context of spmv_hip_create), on formats 7 to 10");
+    if (c->format < 7 || c->format > 10) {
+        const std::string text = (c->format == 0 ? std::string("no matrix uploaded (format 0)") : "the context holds format " + std::to_string(c->format)) +
+            ": spmv_hip_run_scaled needs format 7 (fp32 values), 8, 9 or 10 (compact)";
+        return fail(SPMV_HIP_ERR_STATE, text.c_str());
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const bool timed = !(c->flags & SPMV_HIP_FLAG_NO_RUN_EVENTS);
+    if (timed)
+        HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    int rc = SPMV_HIP_OK;
+    switch (c->format) {
+    case 7: rc = spmv_hip_csr_spmv_f32_scaled(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
+    case 8: rc = spmv_hip_csr_spmv_c16_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
+    case 9: rc = spmv_hip_csr_spmv_c16_f64_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
+    default: rc = spmv_hip_csr_spmv_c16_f32xy_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, alpha, beta, c->d_y32, c->d_y32, c->stream); break;
+    }
+    if (rc != 0)
+        return rc;
+    if (timed) {
+        HIP_TRY(hipEventRecord(c->ev1, c->stream));
+        c->timed = true;
+    }
+    return SPMV_HIP_OK;
+}
+
 int spmv_hip_sync(spmv_hip_ctx * c)
 {
     if (!c)

@@ -80,11 +80,11 @@ struct CompactSource {
 };
 
 // One wave of any kernel below: its tile's window table into the wave's LDS slot, then the tile over V values and T vectors.
-template <bool X32, class V, class T>
+template <bool X32, class V, class T, class Rows>
 __device__ __forceinline__ void compact_wave(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,
                                              const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,
                                              const int32_t * __restrict__ j, const V * __restrict__ a, const T * __restrict__ x,
-                                             T * y, int exact_order)
+                                             const Rows out, int exact_order)
 {
     __shared__ __attribute__((aligned(16))) double prod_all[4][kF32Tile + 4];
     __shared__ int tab_all[4][8];
@@ -106,7 +106,7 @@ __device__ __forceinline__ void compact_wave(int ntiles, const int4 * __restrict
     }
     // the tile's codes start at quad t.w with the slot of entry k0 & ~3
     const CompactSource src{compact, (t.meta & kC16MetaOneWindow) != 0, codes + 4 * (size_t) (unsigned) t.w - (t.k0 & ~3), tab, base0, WideSource{j}};
-    f32_tile<X32>(prod_all[wave], t, src, p, a, x, y, exact_order);
+    f32_tile<X32>(prod_all[wave], t, src, p, a, x, out, exact_order);
 }
 
 template <bool X32>
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 8) void csr_compact_kernel(int ntiles, const i
                                                              const int32_t * __restrict__ j, const float * __restrict__ a,
                                                              const double * __restrict__ x, double * y, int exact_order)
 {
-    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
+    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, AccumulateRows<double>{y}, exact_order);
 }
 
 // y += A x: the fp64 values of the caller beside the codes
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256, 8) void csr_compact_f64_kernel(int ntiles, con
                                                                  const int32_t * __restrict__ j, const double * __restrict__ a,
                                                                  const double * __restrict__ x, double * y, int exact_order)
 {
-    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
+    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, AccumulateRows<double>{y}, exact_order);
 }
 
 // y <- fl32(y + fl32(A) x): float x and y beside the float values and the codes; X32: cols * 4 < 2^32
@@ -135,8 +135,24 @@ __global__ __launch_bounds__(256, 8) void csr_compact_f32xy_kernel(int ntiles, c
                                                                    const int32_t * __restrict__ j, const float * __restrict__ a,
                                                                    const float * __restrict__ x, float * y, int exact_order)
 {
-    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, y, exact_order);
+    compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, AccumulateRows<float>{y}, exact_order);
 }
+
+// ---- y_out <- alpha A x + beta y_in (include/spmv_hip_scaled.h): the three kernels above with the scaled epilogue of
+// csr_f32values.hpp (ScaledRows); BETA0: beta == 0, y_in is not loaded.  The LDS is the sibling's: compact_wave's.
+#define SPMV_C16_SCALED_KERNEL(NAME, V, T)                                                                                                  \
+    template <bool X32, bool BETA0>                                                                                                        \
+    __global__ __launch_bounds__(256, 8) void NAME(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,            \
+                                                   const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,                    \
+                                                   const int32_t * __restrict__ j, const V * __restrict__ a, const T * __restrict__ x,     \
+                                                   double alpha, double beta, const T * y_in, T * y_out, int exact_order)                  \
+    {                                                                                                                                      \
+        compact_wave<X32>(ntiles, desc, bases, codes, p, j, a, x, ScaledRows<T, BETA0>{alpha, beta, y_in, y_out}, exact_order);            \
+    }
+SPMV_C16_SCALED_KERNEL(csr_compact_scaled_kernel, float, double)
+SPMV_C16_SCALED_KERNEL(csr_compact_f64_scaled_kernel, double, double)
+SPMV_C16_SCALED_KERNEL(csr_compact_f32xy_scaled_kernel, float, float)
+#undef SPMV_C16_SCALED_KERNEL
 
 // spmv_hip_c16_plan_verify: a wave per tile; every entry of a compact tile decoded and compared with the caller's column
 static __global__ __launch_bounds__(256) void c16_verify_kernel(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,

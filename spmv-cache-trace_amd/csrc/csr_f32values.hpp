@@ -179,10 +179,44 @@ __device__ __forceinline__ F32Tile load_f32_tile(const int4 * __restrict__ desc,
                    __builtin_amdgcn_readfirstlane(dp.d0.w), __builtin_amdgcn_readfirstlane(dp.d1.x), __builtin_amdgcn_readfirstlane(dp.d1.y)};
 }
 
-// One tile by one wave; prod is the wave's LDS slice (kF32Tile + 4 doubles), src the kernel's column source.
-template <bool X32, class Source, class V, class T>
+// What a tile does with a row's sum z: its EPILOGUE (include/spmv_hip_scaled.h).  Every row's sum is formed once, by one lane,
+// so the epilogue is that lane's: old(i) is what it reads of row i beforehand (the stream tile asks early, beside its loads),
+// store(i, old, z) the row's one store.
+//     AccumulateRows            y[i] <- (T)(y[i] + z): every multiply that is y += A x
+//     ScaledRows<T, false>      y_out[i] <- (T)(fl(alpha z) + fl(beta y_in[i])): two multiplies and an add, each rounded
+//     ScaledRows<T, true>       y_out[i] <- (T) fl(alpha z): beta == 0, and y_in is not a load that is skipped but no load at all
+// alpha and beta are kernel arguments: wave-uniform, in scalar registers.  y_in may be y_out (a row is read and written by the
+// same lane) and is not __restrict__.
+template <class T>
+struct AccumulateRows {
+    T * y;
+    __device__ __forceinline__ double old(int i) const { return (double) y[i]; }
+    __device__ __forceinline__ void store(int i, double yv, double z) const { y[i] = (T) (yv + z); }
+};
+template <class T, bool BETA0>
+struct ScaledRows {
+    double alpha, beta;
+    const T * y_in;
+    T * y_out;
+    __device__ __forceinline__ double old(int i) const
+    {
+        if (BETA0)
+            return 0.0;
+        return (double) y_in[i];
+    }
+    __device__ __forceinline__ void store(int i, double yv, double z) const
+    {
+        if (BETA0)
+            y_out[i] = (T) (alpha * z);
+        else
+            y_out[i] = (T) (alpha * z + beta * yv);
+    }
+};
+
+// One tile by one wave; prod is the wave's LDS slice (kF32Tile + 4 doubles), src the kernel's column source, out the epilogue.
+template <bool X32, class Source, class V, class T, class Rows>
 __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const Source src, const int32_t * __restrict__ p,
-                                         const V * __restrict__ a, const T * __restrict__ x, T * y, int exact_order)
+                                         const V * __restrict__ a, const T * __restrict__ x, const Rows out, int exact_order)
 {
     constexpr int TILE = kF32Tile, QUADS = TILE / 256;
     const int lane = (int) __lane_id();
@@ -206,7 +240,7 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             ps = pt[rowi];
             pe = pt[rowi + 1];
         }
-        const double yv = (double) y[r0 + rowi];
+        const double yv = out.old(r0 + rowi);
         const int last = (k1 - 1 - kb) & ~3;
         src.template products<QUADS, X32>(prod, a + kb, x, kb, last, lane);
         wave_lds_fence();
@@ -226,7 +260,7 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             }
         }
         if (sub < nrows && part == 0)
-            y[r0 + sub] = (T) (yv + z);
+            out.store(r0 + sub, yv, z);
     } else if (k1 - kb <= TILE) {
         // ---- a tile of empty rows, or the tile whose last quad is not whole (the ragged end of the arrays): entry by entry,
         // one lane per row, left to right
@@ -238,13 +272,13 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             double z = 0.0;
             for (int k = s; k < e_row; ++k)
                 z += prod[k];
-            y[r0 + r] = (T) ((double) y[r0 + r] + z);
+            out.store(r0 + r, out.old(r0 + r), z);
         }
     } else if (!exact_order) {
         // ---- one row longer than a tile: the whole wave, in registers ----
         const double z = src.template long_row<X32>(a, x, k0, k1, lane);
         if (lane == 0)
-            y[r0] = (T) ((double) y[r0] + z);
+            out.store(r0, out.old(r0), z);
     } else {
         // ---- ... in the reference's order: lane 0 adds tiles of products left to right ----
         double z = 0.0;
@@ -259,7 +293,7 @@ __device__ __forceinline__ void f32_tile(double * prod, const F32Tile t, const S
             wave_lds_fence();
         }
         if (lane == 0)
-            y[r0] = (T) ((double) y[r0] + z);
+            out.store(r0, out.old(r0), z);
     }
 }
 
@@ -273,7 +307,40 @@ __global__ __launch_bounds__(256, 8) void csr_f32values_kernel(int ntiles, const
     const int w = (int) blockIdx.x * 4 + wave;
     if (w >= ntiles)
         return; // whole wave leaves; no workgroup barrier in this kernel
-    f32_tile<X32>(prod_all[wave], load_f32_tile(desc, w), WideSource{j}, p, a, x, y, exact_order);
+    f32_tile<X32>(prod_all[wave], load_f32_tile(desc, w), WideSource{j}, p, a, x, AccumulateRows<double>{y}, exact_order);
+}
+
+// y_out <- alpha fl32(A) x + beta y_in (include/spmv_hip_scaled.h): the same tile with the scaled epilogue; BETA0: beta == 0
+template <bool X32, bool BETA0>
+__global__ __launch_bounds__(256, 8) void csr_f32values_scaled_kernel(int ntiles, const int4 * __restrict__ desc, const int32_t * __restrict__ p,
+                                                                      const int32_t * __restrict__ j, const float * __restrict__ a,
+                                                                      const double * __restrict__ x, double alpha, double beta,
+                                                                      const double * y_in, double * y_out, int exact_order)
+{
+    __shared__ __attribute__((aligned(16))) double prod_all[4][kF32Tile + 4];
+    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
+    const int w = (int) blockIdx.x * 4 + wave;
+    if (w >= ntiles)
+        return; // whole wave leaves; no workgroup barrier in this kernel
+    f32_tile<X32>(prod_all[wave], load_f32_tile(desc, w), WideSource{j}, p, a, x, ScaledRows<double, BETA0>{alpha, beta, y_in, y_out}, exact_order);
+}
+
+// The scaled multiplies where no tile runs -- alpha == 0, or a plan without tiles (rows, cols or nnz of zero): a lane per row,
+//     y_out[i] <- (T)(fl(alpha * +0.0) + fl(beta y_in[i]))     ZTERM: alpha != 0, every row sum is +0.0
+//     y_out[i] <- (T) fl(beta y_in[i])                         alpha == 0
+// and without the beta term (and without a load of y_in) where BETA0; alpha == 0 and beta == 0 store +0.0.
+template <class T, bool BETA0, bool ZTERM>
+__global__ __launch_bounds__(256) void scaled_rows_only_kernel(int rows, double alpha, double beta, const T * y_in, T * y_out)
+{
+    const int i = (int) blockIdx.x * 256 + (int) threadIdx.x;
+    if (i >= rows)
+        return;
+    double r = 0.0;
+    if (ZTERM)
+        r = alpha * 0.0;
+    if (!BETA0)
+        r = ZTERM ? r + beta * (double) y_in[i] : beta * (double) y_in[i];
+    y_out[i] = (T) r;
 }
 
 // spmv_hip_narrow_values: out[k] = (float) value[k]; per workgroup {values that changed, finite values that became infinite,

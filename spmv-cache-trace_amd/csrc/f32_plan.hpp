@@ -36,4 +36,19 @@ NarrowResult narrow_host(int64_t n, const double * value, float * out);
 // what an upload refuses: finite values that are infinite as floats, and -- unless allow_rounding -- values that are not floats
 int narrow_refusal(NarrowResult const & c, int allow_rounding);
 
+// ---- y_out <- alpha A x + beta y_in (include/spmv_hip_scaled.h): what the four scaled multiplies share -------------------------------
+
+// the scale of one call; a multiply without one (y += A x) passes none
+template <class T>
+struct ScaledArgs {
+    double alpha, beta;
+    const T * y_in;
+};
+
+// y_in and y_out of a scaled call over `rows` elements of `elem` bytes: y_out null, y_in null where it is read (beta != 0), the
+// two overlapping without being the same array, or float vectors off their 4-byte alignment
+int scaled_vectors_check(int32_t rows, size_t elem, double beta, const void * y_in, const void * y_out);
+// the call where no tile runs (alpha == 0, or a plan without tiles: zterm says that alpha * +0.0 is still added): one vector kernel
+int scaled_rows_only(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out, hipStream_t s);
+
 } // namespace spmvi

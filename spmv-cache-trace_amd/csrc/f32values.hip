@@ -65,6 +65,60 @@ int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_er
     return SPMV_HIP_OK;
 }
 
+// spmv_hip_csr_spmv_f32 (scale null: y += fl32(A) x) and spmv_hip_csr_spmv_f32_scaled (d_y is y_out): one set of refusals
+int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                 const double * d_x, double * d_y, void * stream, const ScaledArgs<double> * scale)
+{
+    if (!pl)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    if (d_x && (const void *) d_x == (const void *) d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (scale) {
+        const int rc = scaled_vectors_check(pl->rows, sizeof(double), scale->beta, scale->y_in, d_y);
+        if (rc != 0 || pl->rows == 0)
+            return rc;
+        if (scale->alpha == 0.0 || pl->ntiles == 0) // the beta part alone: neither the matrix nor x is read
+            return scaled_rows_only(pl->rows, false, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, s);
+    }
+    if (pl->ntiles == 0) // rows, cols or nnz of zero
+        return SPMV_HIP_OK;
+    if (!d_row_ptr || !d_column_index || !d_value || !d_x || !d_y)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
+    if (!aligned16(d_column_index) || !aligned16(d_value))
+        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
+    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
+    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
+    const bool x32 = (long long) pl->cols * 8 < (1LL << 32);
+    if (scale) {
+        void (*kernel)(int, const int4 *, const int32_t *, const int32_t *, const float *, const double *, double, double, const double *, double *, int);
+        if (scale->beta == 0.0)
+            kernel = x32 ? spmv::csr_f32values_scaled_kernel<true, true> : spmv::csr_f32values_scaled_kernel<false, true>;
+        else
+            kernel = x32 ? spmv::csr_f32values_scaled_kernel<true, false> : spmv::csr_f32values_scaled_kernel<false, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, scale->alpha, scale->beta,
+                           scale->y_in, d_y, exact);
+    } else if (x32)
+        hipLaunchKernelGGL(spmv::csr_f32values_kernel<true>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
+    else
+        hipLaunchKernelGGL(spmv::csr_f32values_kernel<false>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
+template <class T>
+int rows_only(int32_t rows, bool zterm, double alpha, double beta, const T * y_in, T * y_out, hipStream_t s)
+{
+    void (*kernel)(int, double, double, const T *, T *);
+    if (beta == 0.0)
+        kernel = zterm ? spmv::scaled_rows_only_kernel<T, true, true> : spmv::scaled_rows_only_kernel<T, true, false>;
+    else
+        kernel = zterm ? spmv::scaled_rows_only_kernel<T, false, true> : spmv::scaled_rows_only_kernel<T, false, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned) (((long long) rows + 255) / 256)), dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
 } // namespace
 
 // ---- what compact.hip shares (f32_plan.hpp) ------------------------------------------------------------------------------------
@@ -172,6 +226,31 @@ int narrow_refusal(NarrowResult const & c, int allow_rounding)
     return fail(SPMV_HIP_ERR_INVALID, text);
 }
 
+int scaled_vectors_check(int32_t rows, size_t elem, double beta, const void * y_in, const void * y_out)
+{
+    if (rows == 0)
+        return SPMV_HIP_OK;
+    if (!y_out)
+        return fail(SPMV_HIP_ERR_INVALID, "d_y_out is null");
+    const uintptr_t in = reinterpret_cast<uintptr_t>(y_in), out = reinterpret_cast<uintptr_t>(y_out), bytes = (uintptr_t) rows * elem;
+    if (elem == 4 && ((out | (beta != 0.0 ? in : 0)) & 3u))
+        return fail(SPMV_HIP_ERR_ALIGN, "d_y_in and d_y_out must be 4-byte aligned");
+    if (beta == 0.0) // y_in is never read
+        return SPMV_HIP_OK;
+    if (!y_in)
+        return fail(SPMV_HIP_ERR_INVALID, "d_y_in is null and beta is not 0");
+    if (in != out && in < out + bytes && out < in + bytes)
+        return fail(SPMV_HIP_ERR_INVALID, "d_y_in and d_y_out overlap without being the same array");
+    return SPMV_HIP_OK;
+}
+
+int scaled_rows_only(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out, hipStream_t s)
+{
+    if (float_vectors)
+        return rows_only(rows, zterm, alpha, beta, static_cast<const float *>(y_in), static_cast<float *>(y_out), s);
+    return rows_only(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), s);
+}
+
 } // namespace spmvi
 
 extern "C" {
@@ -268,25 +347,15 @@ int spmv_hip_f32_plan_csr(spmv_hip_f32_plan ** plan, int32_t rows, int32_t cols,
 int spmv_hip_csr_spmv_f32(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
                           const float * d_value, const double * d_x, double * d_y, void * stream)
 {
-    if (!pl)
-        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
-    if (d_x && (const void *) d_x == (const void *) d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
-    if (pl->ntiles == 0) // rows, cols or nnz of zero
-        return SPMV_HIP_OK;
-    if (!d_row_ptr || !d_column_index || !d_value || !d_x || !d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
-    if (!aligned16(d_column_index) || !aligned16(d_value))
-        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
-    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
-    if ((long long) pl->cols * 8 < (1LL << 32))
-        hipLaunchKernelGGL(spmv::csr_f32values_kernel<true>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
-    else
-        hipLaunchKernelGGL(spmv::csr_f32values_kernel<false>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream, nullptr);
+}
+
+int spmv_hip_csr_spmv_f32_scaled(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
+                                 const float * d_value, const double * d_x, double alpha, double beta, const double * d_y_in,
+                                 double * d_y_out, void * stream)
+{
+    const ScaledArgs<double> scale{alpha, beta, d_y_in};
+    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale);
 }
 
 int spmv_hip_f32_plan_info(const spmv_hip_f32_plan * pl, int64_t * out, int n)

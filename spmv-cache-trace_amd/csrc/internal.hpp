@@ -24,6 +24,7 @@
 #include "spmv_hip_compact.h"
 #include "spmv_hip_compact_f64.h"
 #include "spmv_hip_compact_f32xy.h"
+#include "spmv_hip_scaled.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1

@@ -12,6 +12,7 @@
 #include "spmv_hip_compact.h"
 #include "spmv_hip_compact_f64.h"
 #include "spmv_hip_compact_f32xy.h"
+#include "spmv_hip_scaled.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
@@ -362,7 +363,10 @@ public:
     void run(TraceConfig const &) override
     {
         if (is_master()) {
-            check(spmv_hip_run(ctx), "run");
+            if (options.scaled) // --alpha / --beta (the float-tile kernels only: main.cpp refuses them elsewhere)
+                check(spmv_hip_run_scaled(ctx, options.alpha, options.beta), "run_scaled");
+            else
+                check(spmv_hip_run(ctx), "run");
             check(spmv_hip_sync(ctx), "sync");
             std::uint64_t ns = 0, gns = 0;
             if (spmv_hip_last_run_times(ctx, &ns, &gns) == SPMV_HIP_OK) {
@@ -411,6 +415,18 @@ protected:
             throw kernel_error(matrix_path + ": " + spmv_hip_strerror(rc) + (detail.empty() ? "" : ": " + detail) +
                                " (" + what + ")");
         }
+    }
+
+    // --alpha / --beta: the scale of every run, in the kernel section (nothing without the options)
+    std::ostream & print_scale(std::ostream & o) const
+    {
+        if (options.scaled) {
+            std::ostringstream t;
+            t.precision(17);
+            t << ",\n\"alpha\": " << options.alpha << ",\n\"beta\": " << options.beta;
+            o << t.str();
+        }
+        return o;
     }
 
     std::ostream & print_device(std::ostream & o) const
@@ -580,7 +596,7 @@ public:
     {
         print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
         o << ",\n\"value_bytes\": 4,\n\"values_inexact\": " << inexact << ",\n\"max_value_rounding\": " << max_rounding;
-        return print_device(o) << "\n}";
+        return print_device(print_scale(o)) << "\n}";
     }
 
     double flops_per_run() const override { return 2.0 * A.num_entries; }
@@ -675,7 +691,7 @@ public:
         print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
         o << ",\n\"value_bytes\": 4" << (f32xy() ? ",\n\"vector_bytes\": 4" : "") << ",\n\"values_inexact\": " << inexact << ",\n\"max_value_rounding\": " << max_rounding
           << ",\n\"compact_tiles\": " << compact_tiles << ",\n\"wide_tiles\": " << wide_tiles << ",\n\"streamed_bytes\": " << streamed;
-        return print_device(o) << "\n}";
+        return print_device(print_scale(o)) << "\n}";
     }
 
     double flops_per_run() const override { return 2.0 * A.num_entries; }
@@ -729,7 +745,7 @@ public:
         print_common(o, name(), matrix_path, "csr", A.rows, A.columns, A.num_entries, A.size());
         o << ",\n\"value_bytes\": 8,\n\"compact_tiles\": " << compact_tiles << ",\n\"wide_tiles\": " << wide_tiles
           << ",\n\"streamed_bytes\": " << streamed;
-        return print_device(o) << "\n}";
+        return print_device(print_scale(o)) << "\n}";
     }
 
     double flops_per_run() const override { return 2.0 * A.num_entries; }

@@ -98,6 +98,8 @@ enum Key
     key_transpose,
     key_f32_values,
     key_compact,
+    key_alpha,
+    key_beta,
 };
 
 bool parse_count(char const * arg, long long & out)
@@ -221,9 +223,23 @@ error_t parse_option(int key, char * arg, argp_state * state)
         else if (!std::strcmp(arg, "f32")) a.spmv.compact = 4;
         else argp_error(state, "compact: expected 'round' (the default) or 'exact', or 'f64', or 'f32'");
         break;
+    case key_alpha:
+    case key_beta: {
+        char * end = nullptr;
+        errno = 0;
+        double const value = std::strtod(arg, &end);
+        if (errno != 0 || end == arg || *end != '\0')
+            argp_error(state, key == key_alpha ? "alpha: expected a number" : "beta: expected a number");
+        (key == key_alpha ? a.spmv.alpha : a.spmv.beta) = value;
+        a.spmv.scaled = true;
+        break;
+    }
     case ARGP_KEY_END:
         if (a.list_perf_events)
             break;
+        if (a.spmv.scaled && !a.spmv.f32_values && !a.spmv.compact)
+            argp_error(state, "--alpha / --beta need --f32-values or --compact[=f64|f32]: only the multiplies over float tiles have a scaled "
+                              "form, y <- alpha A x + beta y (spmv_hip_run_scaled)");
         if (a.spmv.compact) {
             // what --compact runs on: hip-csr on one device (include/spmv_hip_compact.h); anything else is refused here rather
             // than multiplied some other way
@@ -417,6 +433,11 @@ int main(int argc, char ** argv)
          "and y stored as 4-byte floats on the device as well, every row's fp64 sum rounded to float once per run (kernel "
          "hip-csr-spmv-compact-f32); --check compares with the CPU CSR kernel on the values and x rounded to float on the host, "
          "with a tolerance that grows with the number of runs", 2},
+        {"alpha", key_alpha, "A", 0,
+         "EXTENSION (with --f32-values or --compact[=f64|f32]): every run is y <- A * (matrix x) + B * y instead of y += matrix x, in "
+         "one launch (spmv_hip_run_scaled); A and B default to 1, and the JSON document names both.  --check compares with the CPU "
+         "CSR kernel's product put through the same number of scaled steps on the host", 2},
+        {"beta", key_beta, "B", 0, "EXTENSION: see --alpha", 2},
         {"vectors", key_vectors, "K", 0,
          "EXTENSION (hip-csr, one device): Y += A X for K = 1 ... 16 vectors in one multiply, every stored entry read once; column c "
          "of X is x scaled by c + 1.  Flops count 2 nnz K; --check compares every column with the CPU CSR kernel", 2},
@@ -602,6 +623,7 @@ int main(int argc, char ** argv)
                 ref_options.round_values_on_host = true;
             }
             ref_options.vectors = 0;
+            ref_options.scaled = false; // (--alpha / --beta: the CPU kernel multiplies once, and the scaled steps are restated below)
             double err = 0.0;
             int const k = std::max(1, args.spmv.vectors);
             std::vector<double> const got = kernel->result();
@@ -618,15 +640,28 @@ int main(int argc, char ** argv)
                             e = static_cast<double>(static_cast<float>(e));
                     ref->set_x(xc);
                 }
-                for (int r = 0; r < args.profile + 1; ++r)
+                for (int r = 0; r < (args.spmv.scaled ? 1 : args.profile + 1); ++r)
                     ref->run(one);
+                std::vector<double> want = ref->result();
+                if (args.spmv.scaled) {
+                    // y <- alpha z + beta y from y = 0, run by run, with z = A x from the CPU kernel: two products and a sum, each
+                    // rounded; --compact=f32 rounds y to float once per run
+                    std::vector<double> const z = want;
+                    std::fill(want.begin(), want.end(), 0.0);
+                    for (int r = 0; r < args.profile + 1; ++r)
+                        for (std::size_t i = 0; i < want.size(); ++i) {
+                            volatile double const az = args.spmv.alpha * z[i], by = args.spmv.beta * want[i];
+                            double const yi = args.spmv.alpha == 0.0 ? by : (args.spmv.beta == 0.0 ? az : az + by);
+                            want[i] = float_vectors ? static_cast<double>(static_cast<float>(yi)) : yi;
+                        }
+                }
                 std::vector<double> col = got;
                 if (args.spmv.vectors > 0) {
                     col.assign(got.size() / (std::size_t) k, 0.0);
                     for (std::size_t i = 0; i < col.size(); ++i)
                         col[i] = got[i * (std::size_t) k + (std::size_t) c];
                 }
-                double const e = relative_error(col, ref->result());
+                double const e = relative_error(col, want);
                 if (!(e <= err)) // NaN sticks
                     err = e;
             }
@@ -635,7 +670,8 @@ int main(int argc, char ** argv)
                 std::string(args.spmv.transpose ? " on the matrix transposed on the host" : "") +
                 std::string(rounded ? (float_vectors ? " on the values and x rounded to float on the host" : " on the values rounded to float on the host") : "") +
                 (args.spmv.vectors > 0 ? ", every one of the " + std::to_string(k) + " columns" : std::string()) + ", " +
-                std::to_string(args.profile + 1) + " accumulating runs\", \"max_relative_error\": ";
+                std::to_string(args.profile + 1) + (args.spmv.scaled ? " scaled runs (y <- alpha A x + beta y) restated on the host" : " accumulating runs") +
+                "\", \"max_relative_error\": ";
             char buf[64];
             if (std::isnan(err))
                 std::snprintf(buf, sizeof buf, "\"nan\"");

@@ -1,6 +1,6 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
-spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h and spmv_hip_compact_f32xy.h (the C ABI of
-libspmv_hip.so).
+spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h and
+spmv_hip_scaled.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -25,7 +25,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
-                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h")]
+                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -153,6 +153,11 @@ SIGNATURES = {
     "spmv_hip_set_x_f32": (C.c_int, [_vp, _vp]),
     "spmv_hip_set_y_f32": (C.c_int, [_vp, _vp]),
     "spmv_hip_get_y_f32": (C.c_int, [_vp, _vp]),
+    "spmv_hip_csr_spmv_f32_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "spmv_hip_csr_spmv_c16_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "spmv_hip_csr_spmv_c16_f64_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "spmv_hip_csr_spmv_c16_f32xy_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "spmv_hip_run_scaled": (C.c_int, [_vp, C.c_double, C.c_double]),
 }
 
 
@@ -410,6 +415,13 @@ class Context:
     def run(self, runs=1, sync=True):
         for _ in range(runs):
             check(self.lib.spmv_hip_run(self.h))
+        if sync:
+            check(self.lib.spmv_hip_sync(self.h))
+
+    def run_scaled(self, alpha, beta, runs=1, sync=True):
+        """y <- alpha A x + beta y, in place, on a context of formats 7 to 10 (include/spmv_hip_scaled.h)."""
+        for _ in range(runs):
+            check(self.lib.spmv_hip_run_scaled(self.h, alpha, beta))
         if sync:
             check(self.lib.spmv_hip_sync(self.h))
 
@@ -732,6 +744,12 @@ class F32Plan:
         """y += fl32(A) x; raw device addresses, d_val32 a float array, d_x != d_y."""
         check(self.lib.spmv_hip_csr_spmv_f32(self.h, d_row_ptr, d_col, d_val32, d_x, d_y, stream))
 
+    def spmv_scaled(self, d_row_ptr, d_col, d_val32, d_x, alpha, beta, d_y_in, d_y_out, stream=0):
+        """y_out <- alpha fl32(A) x + beta y_in (include/spmv_hip_scaled.h); d_y_in may be 0 / None where beta == 0, the matrix
+        arrays and d_x where alpha == 0; d_y_in == d_y_out is in place."""
+        check(self.lib.spmv_hip_csr_spmv_f32_scaled(self.h, d_row_ptr or None, d_col or None, d_val32 or None, d_x or None, alpha, beta,
+                                                    d_y_in or None, d_y_out or None, stream))
+
 
 C16_INFO_KEYS = ["rows", "cols", "stored_entries", "flags", "workgroups", "tiles", "compact_tiles", "wide_tiles", "long_row_tiles",
                  "compact_entries"] + ["tiles_with_%d_windows" % w for w in range(1, 9)] + ["device_bytes", "streamed_bytes"]
@@ -814,6 +832,22 @@ class C16Plan:
     def spmv_f32xy(self, d_row_ptr, d_col, d_val32, d_x32, d_y32, stream=0):
         """y <- fl32(y + fl32(A) x) through the same plan; d_x32 and d_y32 float arrays (4-byte aligned), otherwise as spmv."""
         check(self.lib.spmv_hip_csr_spmv_c16_f32xy(self.h, d_row_ptr, d_col or None, d_val32, d_x32, d_y32, stream))
+
+    def spmv_scaled(self, d_row_ptr, d_col, d_val32, d_x, alpha, beta, d_y_in, d_y_out, stream=0):
+        """y_out <- alpha fl32(A) x + beta y_in (include/spmv_hip_scaled.h); d_y_in may be 0 / None where beta == 0, the matrix
+        arrays and d_x where alpha == 0; d_y_in == d_y_out is in place."""
+        check(self.lib.spmv_hip_csr_spmv_c16_scaled(self.h, d_row_ptr or None, d_col or None, d_val32 or None, d_x or None, alpha, beta,
+                                                    d_y_in or None, d_y_out or None, stream))
+
+    def spmv_f64_scaled(self, d_row_ptr, d_col, d_val, d_x, alpha, beta, d_y_in, d_y_out, stream=0):
+        """y_out <- alpha A x + beta y_in on fp64 values through the same plan, otherwise as spmv_scaled."""
+        check(self.lib.spmv_hip_csr_spmv_c16_f64_scaled(self.h, d_row_ptr or None, d_col or None, d_val or None, d_x or None, alpha, beta,
+                                                        d_y_in or None, d_y_out or None, stream))
+
+    def spmv_f32xy_scaled(self, d_row_ptr, d_col, d_val32, d_x32, alpha, beta, d_y_in32, d_y_out32, stream=0):
+        """y_out <- fl32(alpha fl32(A) x + beta y_in) on float vectors through the same plan, otherwise as spmv_scaled."""
+        check(self.lib.spmv_hip_csr_spmv_c16_f32xy_scaled(self.h, d_row_ptr or None, d_col or None, d_val32 or None, d_x32 or None, alpha, beta,
+                                                          d_y_in32 or None, d_y_out32 or None, stream))
 
     def verify(self, d_col, stream=0):
         """How many entries of compact tiles decode to a column other than d_col's (the content guard)."""
