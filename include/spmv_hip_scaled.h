@@ -15,6 +15,10 @@
  *                (the kernel has no load of y_in).  This is q = A p without a memset of q.
  *   alpha == 0   no tile is launched and neither the matrix nor x is read; d_row_ptr, d_column_index, d_value and d_x may be
  *                null: y_out[i] <- (T) fl(beta * (double) y_in[i]), and +0.0 where beta == 0 as well.  One small vector kernel.
+ *   -0.0         counts as zero for both factors (the comparisons are ==): y_in is not read under beta == -0.0, no tile runs
+ *                under alpha == -0.0, and alpha == -0.0 with beta == -0.0 stores +0.0.  Every other factor, NaN and +-Inf
+ *                included, goes through the formula: alpha < 0 with beta == 0 gives -0.0 in a row without entries, an infinite
+ *                alpha gives NaN there (fl(alpha * +0.0)).
  *   alpha = 1, beta = 1, y_in == y_out   the bits of the multiply without a scale.
  *   alpha = -1, beta = 1, y_in = b       the residual r = b - A x, out of place.
  *

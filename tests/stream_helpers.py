@@ -1,6 +1,7 @@
 """What test_gpu_streams.py is made of: a non-blocking side stream with a calibrated delay in front of it, device arrays that
 are first filled with contents that are wrong but safe and get their real contents BEHIND the delay, and one `Case` per multiply
-family (the device arrays, the call, the oracle's answer and its tolerance, the rows whose sums never meet in atomics)."""
+family (the device arrays, the call, the oracle's answer and its tolerance, the rows whose sums never meet in atomics) -- the
+scaled forms of the float-tile multiplies included (ScaledCase)."""
 import ctypes
 import functools
 import math
@@ -14,6 +15,7 @@ import poison
 import test_gpu_nonfinite as nf
 from spmv_amd import capi, synth
 from test_gpu_multivec import _mixed_lengths
+from test_gpu_scaled import restate
 
 HIP_STREAM_NON_BLOCKING = 0x01
 SCRATCH_BYTES = 256 << 20   # one pass of the delay reads and writes this much
@@ -473,6 +475,63 @@ def float_family_case(oracle, family):
             multiply = {"spmv_c16": plan.spmv, "spmv_c16_f64": plan.spmv_f64, "spmv_c16_f32xy": plan.spmv_f32xy}[family]
         case.plans.append(plan)
         return lambda st, xp, yp: multiply(P, C, V, xp, yp, st)
+
+    case.planner = planner
+    return case
+
+
+SCALED_KINDS = ("f32", "c16", "c16_f64", "c16_f32xy")
+
+
+class ScaledCase(Case):
+    """y_out <- alpha A x + beta y_in (include/spmv_hip_scaled.h).  planner() plans and returns the in-place residual step
+    call(stream, x address, y address), y <- y - A x, for the tests that chain accumulating multiplies; case.scaled(stream, x
+    address, alpha, beta, y_in address, y_out address) is the plan's scaled multiply and, for the float pair, case.scaled_c16 the
+    double-vector multiply through the SAME plan.  No atomics in this family: every row is claimed bit for bit."""
+
+    def row_sums(self, x):
+        """(z, (|A||x|)_i): the oracle's CSR kernel run once from y = +0.0."""
+        rows, cols, p, c, v = self.operator
+        x = np.asarray(x, dtype=np.float64)
+        return self.oracle.csr_spmv(rows, p, c, v, x, num_threads=1, runs=1), helpers.abs_products(rows, p, c, v, x)
+
+    def check(self, got, x, y0, runs, same_as, what):
+        """`runs` residual steps in place: bit for bit `same_as`; double vectors within helpers.assert_close of the restatement."""
+        assert same_as is not None
+        assert_rows_bitwise(np.asarray(got), np.asarray(same_as), None, what)
+        if self.xy == np.float64:
+            z, absz = self.row_sums(x.host)
+            want = y0.host
+            for _ in range(runs):
+                want = restate(-1.0, 1.0, z, want, np.float64)
+            helpers.assert_close(got, want, runs * absz + np.abs(y0.host), what=what + " against the restatement", nterms=runs * self.nterms)
+
+
+def scaled_family_case(oracle, kind):
+    """The four scaled float-tile multiplies on mixed_mesh_and_graph: compact and wide tiles in one launch."""
+    rows, cols, p, c, v = cc.matrix("mixed_mesh_and_graph")
+    a32 = nf._f32(v)
+    values = v if kind == "c16_f64" else a32.astype(np.float64)
+    mats = csr_arrays(p, c, values, np.float64 if kind == "c16_f64" else np.float32)
+    case = ScaledCase("spmv_%s_scaled on mixed_mesh_and_graph" % kind, oracle, (rows, cols, p, c, values), mats,
+                      xy=np.float32 if kind == "c16_f32xy" else np.float64)
+    P, C, V = (m.ptr for m in mats)
+
+    def planner():
+        if kind == "f32":
+            plan = capi.F32Plan(rows, cols, p, 0, 0)
+            case.info = plan.info()
+            assert case.info["tiles"] > 0
+            multiply = plan.spmv_scaled
+        else:
+            plan = capi.C16Plan(rows, cols, p, c, 0, 0)
+            case.info = plan.info()
+            assert case.info["compact_tiles"] > 100 and case.info["wide_tiles"] > 100, case.info
+            multiply = {"c16": plan.spmv_scaled, "c16_f64": plan.spmv_f64_scaled, "c16_f32xy": plan.spmv_f32xy_scaled}[kind]
+            case.scaled_c16 = lambda st, xp, alpha, beta, yi, yo: plan.spmv_scaled(P, C, V, xp, alpha, beta, yi, yo, st)
+        case.plans.append(plan)
+        case.scaled = lambda st, xp, alpha, beta, yi, yo: multiply(P, C, V, xp, alpha, beta, yi, yo, st)
+        return lambda st, xp, yp: multiply(P, C, V, xp, -1.0, 1.0, yp, yp, st)
 
     case.planner = planner
     return case

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import compact_cases as cc
+import float_edges
 import helpers
 import oracle_py
 from spmv_amd import capi, synth
@@ -247,6 +248,26 @@ def test_sums_are_accumulated_in_fp64_and_rounded_once_to_nearest_even(flags):
     assert_bits32(y, np.array([1.0], dtype=np.float32), "a tie above 1.0")
     y = once([0, 1], [0], [1.0], [2.0 ** -24], [1.0 + 2.0 ** -23])
     assert_bits32(y, np.array([1.0 + 2.0 ** -22], dtype=np.float32), "a tie above 1 + 2^-23")
+
+
+@pytest.mark.parametrize("flags", [0, capi.FLAG_EXACT_ORDER])
+def test_float_denormal_x_and_y_are_neither_flushed_on_the_loads_nor_on_the_store(flags):
+    """float_edges.py's matrix (rows of 0 to 7 entries, one compact long row of 9000, nnz % 4 != 0; values and x non-zero small
+    integers, so every row sum is one exact integer n_i in any order) with x = the integers times 2^-149 and y0 = k 2^-149, k in
+    0 ... 3: y0 + n 2^-149 is a float denormal (or a zero), exact, so both orders give it bit for bit.  A load of x or y0 that
+    flushes denormals gives zeros, a store that flushes gives zeros with the sum's sign."""
+    e = float_edges.edges()
+    e.census()
+    t = e.k_den.astype(np.float64) + e.n * float_edges.DEN
+    want = float_edges.f32(t)
+    assert np.array_equal(want.astype(np.float64), t) and np.all(np.abs(t) < 2.0 ** -126) and np.mean(want != 0) > 0.8
+    dev = Device(e.rows, e.cols, e.p, e.c, e.a32, e.x_den, e.k_den)
+    with capi.C16Plan(e.rows, e.cols, e.p, e.c, flags, dev.stream) as plan:
+        info = plan.info()
+        assert info["long_row_tiles"] == 1 and info["stored_entries"] % 4 != 0 and info["wide_tiles"] == 0
+        assert_bits32(dev.run(plan, runs=1), want, "float_edges, flags %d: denormal x and y0" % flags)
+        # three accumulating runs: y0 + 3 n 2^-149, every intermediate a denormal
+        assert_bits32(dev.run(plan), float_edges.f32(t + 2 * e.n * float_edges.DEN), "float_edges, flags %d: three accumulating runs" % flags)
 
 
 def test_spmv_c16_f32xy_refuses_x_equal_y_and_misaligned_arrays():

@@ -9,6 +9,10 @@ a dropped block entry or a neighbour's quad by zero turns a finite row into NaN;
 finite.  Classes are compared exactly; finite rows bitwise with the same plan's result on the clean operand wherever no partial
 sums meet in atomics (there: helpers.assert_close against the oracle).
 
+The scaled forms y_out <- alpha A x + beta y_in of the float-tile multiplies (include/spmv_hip_scaled.h) are multiplies of the
+library too: their epilogue reads y_in through a clamped row, beta == 0 must not load y_in at all and alpha == 0 must not form
+0 * Inf.  Their reference is test_gpu_scaled.restate on the oracle's row sums of the poisoned operand.
+
 Three poisons per case: x by the poison rule (each column with probability min(0.25, 0.3 / mean row length), plus columns 0 and
 cols - 1), the first and last stored entry of every 37th non-empty row, every 29th row of y0.  Before the GPU is looked at the
 oracle's own result must show >= 5 % non-finite rows, >= 50 % finite rows and >= 5 % finite rows beside a non-finite one.
@@ -29,6 +33,7 @@ from spmv_amd import capi, hostapi, synth
 from test_gpu_blocktiles import _scatter_nodes, fem3, fem_ragged
 from test_gpu_multivec import _mixed_lengths
 from test_gpu_plan_handoffs import mesh_case
+from test_gpu_scaled import restate
 from test_gpu_stencil_chunks import grid as grid_with_holes
 from test_gpu_stencil_runs import band, grid2d
 from test_gpu_stencil_sweep import pattern_matrix
@@ -684,3 +689,191 @@ def test_float_value_families(oracle, name):
                     XP.assert_guards(tag)
     for m, mv in mats.values():
         m.assert_unchanged(name)
+
+
+# ---- the scaled forms of the float-value families: y_out <- alpha A x + beta y_in ---------------------------------------------------
+
+SCALED_KINDS = {"f32": "f32values", "c16": "f32values", "c16_f64": "f64values", "c16_f32xy": "f32xy"}  # kind: its operand set
+# (alpha, beta, in place): the residual form both ways; y_in kept beside a NaN-filled y_out; beta == 0, no load of y_in; alpha == 0,
+# no tile and no product with a row sum
+SCALED_PAIRS = [(-1.0, 1.0, True), (-1.0, 1.0, False), (0.375, -2.5, False), (1.0, 0.0, False), (0.0, 0.5, False)]
+BOTH = "poisoned x, +Inf in y_in where the row sum is +Inf"
+SCALED_UPLOADS = {"f32": ("upload_csr_f32values", 7), "c16": ("upload_csr_compact", 8), "c16_f64": ("upload_csr_compact_f64", 9),
+                  "c16_f32xy": ("upload_csr_compact_f32xy", 10)}
+
+
+@functools.lru_cache(maxsize=1)
+def _scaled_sets(oracle, name):
+    """The three operand sets of test_float_value_families for `name`, each with z -- the oracle's CSR kernel run once from
+    y = +0.0 -- on the clean operand, on the poisoned x and on the poisoned values."""
+    rows, cols, p, c, v = cc.matrix(name)
+    a32 = _f32(v)
+    assert np.all(a32 != 0)
+    wide = a32.astype(np.float64)
+    x32 = _f32(synth.x_vector(cols, seed=3))
+    y32 = _f32(np.random.default_rng(7).uniform(-1.0, 1.0, size=rows))
+    sets = {"f32values": Operands(oracle, name + " (float values)", rows, cols, p, c, wide),
+            "f64values": Operands(oracle, name + " (fp64 values)", rows, cols, p, c, v),
+            "f32xy": Operands(oracle, name + " (float values, float x and y)", rows, cols, p, c, wide, x=x32, y0=y32)}
+    for ops in sets.values():
+        mul = lambda val, xx: oracle.csr_spmv(rows, p, c, val, np.asarray(xx, dtype=np.float64), num_threads=1, runs=1)
+        ops.z, ops.z_x, ops.z_v = mul(ops.v, ops.x), mul(ops.v, ops.xp), mul(ops.vp, ops.x)
+        assert np.all(np.isfinite(ops.z))
+        # for the residual form: +Inf in y_in on every other row whose poisoned-x sum is +Inf, where -Inf + (+Inf) must give NaN
+        ops.inf_rows = np.nonzero(np.isposinf(ops.z_x))[0][::2]
+        ops.y0_inf = np.array(ops.y0, copy=True)
+        ops.y0_inf[ops.inf_rows] = np.inf
+    return sets
+
+
+def _restated(alpha, beta, z, y_in, dtype):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return restate(alpha, beta, z, y_in, dtype)
+
+
+def _scaled_references(ops, dtype, what):
+    """{(alpha, beta, poison): restate(...) of the oracle's z on that poisoned operand}, and what the references must show before
+    the GPU is looked at.  A non-zero alpha keeps a non-finite row sum non-finite, so the shares of the poisoned x are those of
+    the multiply without a scale; under alpha == 0 no row sum is used and a poisoned x or matrix must leave every row finite."""
+    zs = {"poisoned x": (ops.z_x, ops.y0), "poisoned values": (ops.z_v, ops.y0), "poisoned y_in": (ops.z, ops.y0p)}
+    refs = {(-1.0, 1.0, BOTH): _restated(-1.0, 1.0, ops.z_x, ops.y0_inf, dtype)}
+    assert len(ops.inf_rows) > 0 and np.all(np.isnan(refs[(-1.0, 1.0, BOTH)][ops.inf_rows])), what
+    for alpha, beta, _ in SCALED_PAIRS:
+        for pname, (z, y_in) in zs.items():
+            ref = refs[(alpha, beta, pname)] = _restated(alpha, beta, z, y_in, dtype)
+            tag = "%s, alpha %g, beta %g, %s" % (what, alpha, beta, pname)
+            if pname == "poisoned y_in":
+                assert np.all((poison.classes(ref)[::poison.Y0_ROW_STRIDE] != poison.FINITE) == (beta != 0.0)), tag
+            elif alpha == 0.0:
+                assert np.all(np.isfinite(ref)), tag + ": 0 * Inf in the reference"
+            elif pname == "poisoned x":
+                poison.assert_not_vacuous(ref, tag)
+            else:
+                assert np.all(poison.classes(ref)[ops.value_rows] != poison.FINITE), tag
+    # the residual form turns a +Inf row sum into -Inf, and -Inf + (+Inf) into NaN
+    zc, rc = poison.classes(ops.z_x), poison.classes(refs[(-1.0, 1.0, "poisoned x")])
+    assert np.any(zc == poison.PINF) and np.all(rc[zc == poison.PINF] == poison.NINF), what
+    return refs
+
+
+def _int_bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _scaled_plan(kind, rows, cols, p, c, flags):
+    """(plan, its scaled multiply as call(matrix, x address, alpha, beta, y_in address, y_out address))."""
+    plan = capi.F32Plan(rows, cols, p, flags, _stream()) if kind == "f32" else capi.C16Plan(rows, cols, p, c, flags, _stream())
+    fn = {"f32": "spmv_scaled", "c16": "spmv_scaled", "c16_f64": "spmv_f64_scaled", "c16_f32xy": "spmv_f32xy_scaled"}[kind]
+    return plan, lambda m, x, alpha, beta, y_in, y_out: getattr(plan, fn)(m.p, m.c, m.v, x, alpha, beta, y_in, y_out, _stream())
+
+
+def _reached(name, kind, info):
+    assert info["tiles"] > 0
+    if kind == "f32":
+        if name == "dense_row_9000_compact":
+            assert info["long_row_tiles"] == 1
+        return
+    if name == "mixed_mesh_and_graph":
+        assert info["compact_tiles"] > 100 and info["wide_tiles"] > 100
+    if name == "banded_five_windows":
+        assert info["tiles_with_5_windows"] > 0
+    if name == "dense_row_9000_compact":
+        assert info["long_row_tiles"] == 1 and info["wide_tiles"] == 0
+    if name == "rows_0_to_7_ragged_end":
+        assert info["stored_entries"] % 4 != 0
+
+
+@pytest.mark.parametrize("kind", list(SCALED_KINDS))
+@pytest.mark.parametrize("name", F32_MATRICES)
+def test_scaled_float_value_families(oracle, name, kind):
+    """spmv_hip_csr_spmv_f32_scaled, _c16_scaled, _c16_f64_scaled and _c16_f32xy_scaled (include/spmv_hip_scaled.h), default and
+    exact order, x and y at both alignments, y_out between the guard pattern.  The reference is test_gpu_scaled.restate on the
+    oracle's z of the poisoned operand: the classes follow from the pattern and the signs of alpha and beta alone.  Finite rows
+    are bitwise those of the same plan's scaled call on the clean operand (no atomics in this family: every row) and, under exact
+    order, the restatement's.  The epilogue reads y_in through a clamped row for the lanes beyond a tile's rows: a clamped load
+    that is USED turns a finite neighbour non-finite under (-1, 1), and lets a row of y_in through under (1, 0)."""
+    rows, cols, p, c, v = cc.matrix(name)
+    ops = _scaled_sets(oracle, name)[SCALED_KINDS[kind]]
+    floats = kind == "c16_f32xy"
+    dtype = np.float32 if floats else np.float64
+    refs = _scaled_references(ops, dtype, "%s, %s" % (name, kind))
+    vdt = np.float64 if kind == "c16_f64" else np.float32
+    m, mv = Matrix(rows, cols, p, c, ops.v, values=vdt), Matrix(rows, cols, p, c, ops.vp, values=vdt)
+    for flags in (0, capi.FLAG_EXACT_ORDER):
+        plan, scaled = _scaled_plan(kind, rows, cols, p, c, flags)
+        _reached(name, kind, plan.info())
+        for front in (FRONTS32 if floats else FRONTS64):
+            X, XP = Guarded(ops.x, front), Guarded(ops.xp, front)
+            assert X.ptr % (8 if floats else 16) == (0 if front % 2 == 0 else (4 if floats else 8))
+            poisons = {"poisoned x": (m, XP, ops.y0), "poisoned values": (mv, X, ops.y0), "poisoned y_in": (m, X, ops.y0p),
+                       BOTH: (m, XP, ops.y0_inf)}
+
+            def run(mat, x, y_in, alpha, beta, in_place, tag):
+                if in_place:
+                    Y = Guarded(y_in, front, result=True)
+                    scaled(mat, x.ptr, alpha, beta, Y.ptr, Y.ptr)
+                    Y.assert_guards(tag)
+                    return Y.get()
+                src, out = Guarded(y_in, front), Guarded(np.full(rows, np.nan, dtype=dtype), front, result=True)
+                scaled(mat, x.ptr, alpha, beta, src.ptr, out.ptr)
+                out.assert_guards(tag)
+                src.assert_guards(tag + " (y_in)")
+                assert np.array_equal(_int_bits(src.get()), _int_bits(y_in)), tag + ": y_in changed"  # NaN rows included
+                return out.get()
+
+            for alpha, beta, in_place in SCALED_PAIRS:
+                base = "%s, %s, flags %x, x and y %d bytes into their buffers, alpha %g, beta %g, %s" % (
+                    name, kind, flags, dtype().itemsize * front, alpha, beta, "in place" if in_place else "out of place")
+                clean = run(m, X, ops.y0, alpha, beta, in_place, base + ", clean")
+                assert np.all(np.isfinite(clean)), base + ", clean"
+                if flags:
+                    poison.assert_finite_rows_bitwise(clean, _restated(alpha, beta, ops.z, ops.y0, dtype), clean, base + ", clean, against the restatement")
+                for pname, (mat, x, y_in) in poisons.items():
+                    if (alpha, beta, pname) not in refs:
+                        continue
+                    tag = "%s, %s" % (base, pname)
+                    ref = refs[(alpha, beta, pname)]
+                    got = run(mat, x, y_in, alpha, beta, in_place, tag)
+                    _compare(got, ref, tag, clean, None, None, None, ref if flags else None)
+                    if (alpha == 0.0 and pname != "poisoned y_in") or (beta == 0.0 and pname == "poisoned y_in"):
+                        # 0 * Inf is never formed; no row of y_in reaches y_out, the clamped lanes' included
+                        assert np.all(np.isfinite(got)) and np.array_equal(_int_bits(got), _int_bits(clean)), tag + ": not the clean run's bits"
+            X.assert_guards(name)
+            XP.assert_guards(name)
+        plan.close()
+    m.assert_unchanged(name)
+    mv.assert_unchanged(name)
+
+
+@pytest.mark.parametrize("kind", list(SCALED_KINDS))
+def test_run_scaled_on_a_poisoned_x_is_the_level_2_call(oracle, kind):
+    """spmv_hip_run_scaled with (-1, 1) on contexts of formats 7 to 10: the classes and the finite bits of the Level-2 call."""
+    name = "rows_0_to_7_ragged_end"
+    rows, cols, p, c, v = cc.matrix(name)
+    ops = _scaled_sets(oracle, name)[SCALED_KINDS[kind]]
+    floats = kind == "c16_f32xy"
+    dtype = np.float32 if floats else np.float64
+    ref = _restated(-1.0, 1.0, ops.z_x, ops.y0, dtype)
+    poison.assert_not_vacuous(ref, "%s, %s, level 1" % (name, kind))
+    upload, fmt = SCALED_UPLOADS[kind]
+    m = Matrix(rows, cols, p, c, ops.v, values=np.float64 if kind == "c16_f64" else np.float32)
+    for flags in (0, capi.FLAG_EXACT_ORDER):
+        tag = "%s, %s, flags %x: spmv_hip_run_scaled(-1, 1) on a poisoned x" % (name, kind, flags)
+        with capi.Context(0, flags) as ctx:
+            getattr(ctx, upload)(rows, cols, p, c, ops.v)
+            assert ctx.info()["format"] == fmt
+            (ctx.set_x_f32 if floats else ctx.set_x)(ops.xp)
+            (ctx.set_y_f32 if floats else ctx.set_y)(ops.y0)
+            ctx.run_scaled(-1.0, 1.0)
+            got = (ctx.get_y_f32 if floats else ctx.get_y)()[:rows]
+        plan, scaled = _scaled_plan(kind, rows, cols, p, c, flags)
+        front = (FRONTS32 if floats else FRONTS64)[0]
+        XP, Y = Guarded(ops.xp, front), Guarded(ops.y0, front, result=True)
+        scaled(m, XP.ptr, -1.0, 1.0, Y.ptr, Y.ptr)
+        Y.assert_guards(tag)
+        want = Y.get()
+        plan.close()
+        poison.assert_classes(want, ref, tag + " (level 2 against the restatement)")
+        poison.assert_classes(got, want, tag)
+        poison.assert_finite_rows_bitwise(got, want, ref, tag + " (finite rows against level 2)")

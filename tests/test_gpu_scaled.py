@@ -7,7 +7,11 @@ SPMV_HIP_FLAG_EXACT_ORDER every result is compared BIT FOR BIT with a numpy rest
 on y = +0.0 (the float paths on the narrowed values, f32xy on x widened from float), then alpha * z, beta * y_in and their sum as
 separate numpy operations (no product where alpha or beta is 0, as the header says), rounded to float for f32xy.  Level 2 runs
 with NaN guard elements around x and y_in, sentinels around y_out, and the column and value arrays as views into larger buffers
-whose neighbours hold column 0 and NaN (the guard scheme of test_gpu_compact64.py)."""
+whose neighbours hold column 0 and NaN (the guard scheme of test_gpu_compact64.py).
+
+Scale factors that are themselves NaN, +-Inf, -0.0, denormal or large enough to overflow follow the same restatement on clean
+operands (-0.0 counts as zero for both), and float vectors are held bit for bit at ties, at FLT_MAX and in the float denormals
+(float_edges.py).  Non-finite OPERANDS are test_gpu_nonfinite.py's, the caller's stream test_gpu_streams.py's."""
 import functools
 import json
 import os
@@ -17,8 +21,10 @@ import numpy as np
 import pytest
 
 import compact_cases as cc
+import float_edges
 import helpers
 import oracle_py
+import poison
 from spmv_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -449,6 +455,141 @@ def test_overwrite_and_alpha_0_calls_captured_and_replayed(kind):
         del g
         dev.inputs_unchanged()
         dev.close()
+
+
+# ---- scale factors that are themselves special, on clean operands ------------------------------------------------------------------
+
+NAN, INF, TINY = float("nan"), float("inf"), 2.0 ** -1074  # (the smallest fp64 denormal)
+SPECIAL_PAIRS = ([(a, b) for a in (NAN, INF, -INF, -0.0, -1.0, TINY, 1e308) for b in (0.0, 1.0)] +
+                 [(a, b) for b in (NAN, INF, -0.0, TINY) for a in (0.0, 1.0)])
+
+
+def _restate_quietly(alpha, beta, z, y_in, dtype):
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        return restate(alpha, beta, z, y_in, dtype)
+
+
+def judged_rows(h, kind):
+    """The rows whose class the restatement fixes in default order as well: rows without entries (z_i is +0.0 in any order), and
+    rows whose |z_i| exceeds helpers.assert_close's bound on two summation orders, 2 nterms 2^-53 (|A||x|)_i, so that the sign of
+    z_i -- which decides between +Inf, -Inf and NaN under an infinite alpha -- is that of any order.  At most 1 % are left out."""
+    z, absz = h.z(kind)
+    lens = np.diff(h.p.astype(np.int64))
+    nterms = max(4096, int(lens.max()) if h.rows else 0)
+    keep = (lens == 0) | (np.abs(z) > 2.0 * nterms * 2.0 ** -53 * absz)
+    assert h.rows == 0 or np.mean(~keep) <= 0.01, "%s, %s: %.2f %% of the rows have a sum within the summation bound of zero" % (
+        h.name, kind, 100 * np.mean(~keep))
+    return keep, lens == 0
+
+
+def _same_but_nan_payloads(got, want, what):
+    """Classes exactly, and every row that is not NaN bit for bit (an infinity's sign is its class)."""
+    poison.assert_classes(got, want, what)
+    poison.assert_finite_rows_bitwise(got, want, want, what)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("flags", [0, capi.FLAG_EXACT_ORDER])
+@pytest.mark.parametrize("name", ["empty_rows", "rows_0_to_7_ragged_end", "dense_row_9000_wide", "no_entries"])
+def test_special_scale_factors_follow_the_restatement(name, flags, kind):
+    """alpha in NaN, +-Inf, -0.0, -1, 2^-1074, 1e308 with beta in 0, 1; beta in NaN, +Inf, -0.0, 2^-1074 with alpha in 0, 1.
+    -0.0 counts as zero for both factors: y_in is not read and may be null under beta = -0.0; no tile runs and the matrix and x
+    may be null under alpha = -0.0.  Exact order: classes exactly and every finite row bit for bit the restatement (NaN payloads are
+    not compared).  Default order: classes on judged_rows, bits on the rows without entries, helpers.assert_close where both
+    factors are finite and at most 1 in magnitude, and two identical calls the same bits.  The float pair in default order is the
+    bits of spmv_hip_csr_spmv_c16_scaled through the same plan on the widened operands, rounded once; that fp64 result is judged."""
+    h = host(name)
+    z, absz = h.z(kind)
+    keep, empty = judged_rows(h, kind)
+    exact = bool(flags & capi.FLAG_EXACT_ORDER)
+    # pinned by the restatement before the GPU is looked at: what a row without entries gives
+    if empty.any():
+        y0 = h.vectors(kind)[1]
+        r = _restate_quietly(-1.0, 0.0, z, y0, np.float64)[empty]
+        assert np.all(r == 0) and np.all(np.signbit(r)), "alpha < 0, beta = 0: -0.0 in rows without entries"
+        for a in (INF, -INF):
+            assert np.all(np.isnan(_restate_quietly(a, 0.0, z, y0, np.float64)[empty])), "alpha = +-Inf: fl(alpha * +0.0) is NaN"
+            assert np.all(np.isnan(_restate_quietly(a, 1.0, z, y0, np.float64)[empty]))
+    dev = Dev(h, kind, flags)
+    wide = Dev(h, "c16", flags) if kind == "c16_f32xy" and not exact else None
+    if wide:
+        wide.xh, wide.y0 = dev.xh.astype(np.float64), dev.y0.astype(np.float64)
+        wide.x = Vec(wide.xh, np.float64)
+    longest = int(np.max(np.diff(h.p))) if h.rows else 0
+    for alpha, beta in SPECIAL_PAIRS:
+        tag = "%s, %s, flags %d, alpha %r, beta %r" % (name, kind, flags, alpha, beta)
+        want = _restate_quietly(alpha, beta, z, dev.y0, dev.dtype)
+        y_in, out = dev.vec(dev.y0), dev.out()
+        dev.call(alpha, beta, y_in, out, matrix=alpha != 0.0, x=alpha != 0.0)  # (alpha = -0.0: null matrix and x)
+        got = out.body(tag)
+        _bits(y_in.body(tag), dev.y0, tag + ": y_in changed")
+        if exact:
+            _same_but_nan_payloads(got, want, tag + ": against the restatement")
+        else:
+            y64, want64 = got, want
+            if wide:
+                w_out = wide.out()
+                wide.call(alpha, beta, wide.vec(wide.y0), w_out, matrix=alpha != 0.0, x=alpha != 0.0)
+                y64, want64 = w_out.body(tag), _restate_quietly(alpha, beta, z, dev.y0, np.float64)
+                with np.errstate(over="ignore", under="ignore"):
+                    _same_but_nan_payloads(got, y64.astype(np.float32), tag + ": against spmv_hip_csr_spmv_c16_scaled through the same plan, rounded once")
+            poison.assert_classes(y64[keep], want64[keep], tag + ": rows without entries and rows whose sum is clear of zero")
+            _same_but_nan_payloads(got[empty], want[empty], tag + ": rows without entries against the restatement")
+            if abs(alpha) <= 1.0 and abs(beta) <= 1.0:
+                scale = abs(alpha) * absz + abs(beta) * np.abs(dev.y0.astype(np.float64))
+                helpers.assert_close(y64, want64, scale, what=tag, nterms=max(4096, longest))
+            again = dev.out()
+            dev.call(alpha, beta, y_in, again, matrix=alpha != 0.0, x=alpha != 0.0)
+            assert np.array_equal(again.body(tag).view(np.uint8), got.view(np.uint8)), tag + ": two identical calls"
+        if beta == 0.0:  # -0.0 included: y_in is not read -- it may be null, and full of NaN it leaves no NaN behind
+            for other in (None, dev.vec(np.full(h.rows, np.nan))):
+                o = dev.out()
+                dev.call(alpha, beta, other, o, matrix=alpha != 0.0, x=alpha != 0.0)
+                b = o.body(tag)
+                assert np.array_equal(b.view(np.uint8), got.view(np.uint8)), "%s: y_in %s" % (tag, "null" if other is None else "full of NaN")
+                if alpha == 0.0:
+                    assert not np.any(np.isnan(b)), tag + ": y_in was read"
+    dev.inputs_unchanged()
+    if name == "dense_row_9000_wide" and kind != "f32":
+        assert dev.plan.info()["long_row_tiles"] == 1
+    dev.close()
+    if wide:
+        wide.close()
+
+
+# ---- float vectors at the edges of the float format ----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("flags", [0, capi.FLAG_EXACT_ORDER])
+def test_float_vectors_at_ties_at_flt_max_and_in_the_denormals(flags):
+    """spmv_hip_csr_spmv_c16_f32xy_scaled on float_edges.py's matrix: values and x non-zero small integers, so every row sum is
+    one exact integer n_i in any order and BOTH orders must give t.astype(float32) bit for bit, t = alpha n + beta y_in exact in
+    fp64.  ties: alpha 2^-24 on y_in cycling through 1.0, 1 + 2^-23, 3.0, -1.0 (a product or a store in float would lose the
+    2^-24).  overflow: alpha 2^102 on +-FLT_MAX (n = 1 stays FLT_MAX, n = 2 is the tie and gives Inf).  denormal results: alpha
+    2^-150 on y_in = k 2^-149 (the store's conversion must not flush, -0.0 keeps its sign).  denormal x: x = integers 2^-149,
+    alpha 2^149, beta 0 gives n_i again (a flushed load gives 0).  The census of row kinds is asserted from numpy alone first."""
+    e = float_edges.edges()
+    count = e.census()
+    print("float_edges: %s" % count)
+    calls = e.calls()
+    dev = Dev(e, "c16_f32xy", flags)
+    info = dev.plan.info()
+    assert info["long_row_tiles"] == 1 and info["stored_entries"] % 4 != 0 and info["tiles"] > 1
+    x_int = dev.x
+    for what, (alpha, beta, x, y_in, t) in calls.items():
+        tag = "float_edges, flags %d, %s (alpha %r, beta %r)" % (flags, what, alpha, beta)
+        dev.x, dev.xh = (x_int, e.x32) if x is e.x32 else (dev.vec(x), x)
+        src = None if y_in is None else dev.vec(y_in)
+        want = float_edges.f32(t)
+        out = dev.out()
+        dev.call(alpha, beta, src, out)
+        _bits(out.body(tag), want, tag + ": out of place")
+        if src is not None:
+            _bits(src.body(tag), y_in, tag + ": y_in changed")
+            y = dev.vec(y_in, SENTINEL)
+            dev.call(alpha, beta, y, y)
+            _bits(y.body(tag), want, tag + ": in place")
+        dev.inputs_unchanged()
+    dev.close()
 
 
 # ---- the host program ------------------------------------------------------------------------------------------------------------

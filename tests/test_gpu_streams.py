@@ -1,5 +1,6 @@
 """Every Level-2 entry point works on the CALLER'S stream: ordered on it, asynchronous where the header says so, usable from two
-streams at once, and capturable into a graph.
+streams at once, and capturable into a graph -- the scaled forms of the float-tile multiplies (include/spmv_hip_scaled.h)
+included; their capture, a linear graph of an overwrite and an alpha == 0 call, is test_gpu_scaled.py's.
 
 The rest of the suite hands the library the null stream, which every blocking stream orders itself against: a kernel, copy or
 memset that escaped to another stream could not be seen there.  Here the stream `s` is NON-BLOCKING (asserted through
@@ -36,6 +37,7 @@ import stream_helpers as sh
 import test_gpu_nonfinite as nf
 from spmv_amd import capi, synth
 from stream_helpers import delayed, on_stream, serial
+from test_gpu_scaled import restate
 
 pytestmark = pytest.mark.gpu
 
@@ -122,6 +124,64 @@ def test_float_value_families(oracle, side, family):
     case = sh.float_family_case(oracle, family)
     _ordered(side, case)
     case.close()
+
+
+@pytest.mark.parametrize("kind", sh.SCALED_KINDS)
+def test_scaled_float_value_families(oracle, side, kind):
+    """y_out <- alpha A x + beta y_in (include/spmv_hip_scaled.h), every call behind the delay with every operand -- y_in
+    included -- wrong but safe until the copies behind the delay arrive: the residual form out of place (y_in comes back
+    unchanged), the overwrite form with y_in null, alpha == 0 (scaled_rows_only_kernel alone) and, on a plan without entries,
+    alpha == 1 (that kernel with the alpha * +0.0 term).  Each asynchronous, bit for bit the same plan's serial null-stream
+    result, and within the family's rule of the restatement on the oracle's row sums: helpers.assert_close for double vectors;
+    the float pair is the bits of spmv_hip_csr_spmv_c16_scaled through the same plan on the widened operands, rounded to float
+    once, and that fp64 result is what assert_close judges."""
+    t = _torch()
+    case = sh.scaled_family_case(oracle, kind)
+    case.planner()
+    floats = case.xy == np.float32
+    x, y = case.vectors()
+    y_in, out = sh.operand(y.host), sh.result(np.full(y.shape, np.nan, dtype=case.xy))
+    z, absz = case.row_sums(x.host)
+    if floats:
+        x64, y_in64, out64 = sh.operand(x.host.astype(np.float64)), sh.operand(y.host.astype(np.float64)), sh.result(np.full(y.shape, np.nan))
+
+    def serially(scaled, xa, yi, yo, alpha, beta):
+        for a in (xa, yi, yo):
+            a.put()
+        t.cuda.synchronize()
+        scaled(0, xa.ptr, alpha, beta, yi.ptr if beta != 0.0 else 0, yo.ptr)
+        t.cuda.synchronize()
+        return yo.body(what="serial run")
+
+    for alpha, beta in ((-1.0, 1.0), (1.0, 0.0), (0.0, 0.5)):
+        what = "%s, alpha %g, beta %g" % (case.what, alpha, beta)
+        want = serially(case.scaled, x, y_in, out, alpha, beta)
+        call = lambda st: case.scaled(st, x.ptr, alpha, beta, y_in.ptr if beta != 0.0 else 0, out.ptr)
+        (got, kept), _ = delayed(side, case.mats + [x, y_in, out], call, [out, y_in], what)
+        sh.assert_rows_bitwise(kept, y.host, None, what + ": y_in changed")
+        sh.assert_rows_bitwise(got, want, None, what + " behind the delay")
+        y64 = got
+        if floats:
+            y64 = serially(case.scaled_c16, x64, y_in64, out64, alpha, beta)
+            sh.assert_rows_bitwise(got, y64.astype(np.float32), None, what + ": against spmv_hip_csr_spmv_c16_scaled through the same plan, rounded once")
+        ref = restate(alpha, beta, z, y.host, np.float64)
+        helpers.assert_close(y64, ref, abs(alpha) * absz + abs(beta) * np.abs(y.host.astype(np.float64)), what=what + " against the restatement",
+                             nterms=case.nterms)
+    case.close()
+    # a plan without entries: no tile, the rows-only kernel with its alpha * +0.0 term, behind the delay
+    rows, cols, p, c, v = cc.matrix("no_entries")
+    plan = capi.F32Plan(rows, cols, p, 0, 0) if kind == "f32" else capi.C16Plan(rows, cols, p, c, 0, 0)
+    assert plan.info()["tiles"] == 0
+    scaled = {"f32": plan.spmv_scaled, "c16": plan.spmv_scaled, "c16_f64": getattr(plan, "spmv_f64_scaled", None),
+              "c16_f32xy": getattr(plan, "spmv_f32xy_scaled", None)}[kind]
+    rng = np.random.default_rng(11)
+    x0, b = sh.operand(rng.uniform(-1.0, 1.0, size=cols).astype(case.xy)), sh.operand(rng.uniform(-1.0, 1.0, size=rows).astype(case.xy))
+    r = sh.result(np.full(rows, np.nan, dtype=case.xy))
+    what = "spmv_%s_scaled on no_entries, alpha 1, beta -2.5" % kind
+    (got, kept), _ = delayed(side, [x0, b, r], lambda st: scaled(0, 0, 0, x0.ptr, 1.0, -2.5, b.ptr, r.ptr, st), [r, b], what)
+    sh.assert_rows_bitwise(kept, b.host, None, what + ": y_in changed")
+    sh.assert_rows_bitwise(got, restate(1.0, -2.5, np.zeros(rows), b.host, case.xy), None, what + " against the restatement")
+    plan.close()
 
 
 def _small():
@@ -310,6 +370,8 @@ TWO_STREAM_CASES = {
     "symv": lambda o: sh.symv_case(o, next(iter(nf.SYMV_CASES))),
     "spmv_t": lambda o: sh.spmv_t_case(o, next(iter(nf.SPMV_T_CASES))),
 }
+# the scaled forms: three residual steps y <- y - A x in place per stream
+TWO_STREAM_CASES.update({"spmv_%s_scaled" % kind: (lambda o, kind=kind: sh.scaled_family_case(o, kind)) for kind in sh.SCALED_KINDS})
 
 
 @pytest.mark.parametrize("shared", [False, True], ids=["a plan each", "one plan shared"])
