@@ -130,6 +130,28 @@ void spmv_hip_destroy(spmv_hip_ctx *ctx);
  * slots and gather on a smaller machine -- the arithmetic is the same, the timing means nothing. */
 int spmv_hip_create_multi(spmv_hip_ctx **ctx, int num_gpus, unsigned flags);
 
+/* ---- uploads: what every spmv_hip_upload_* does to the context ---------------------------------------------------
+ * A context holds one matrix.  An upload that succeeds replaces it whatever its format and size were: the old
+ * arrays, plan, vectors and block vectors (spmv_hip_multivec.h) are freed, the sizes of x and y become those of the
+ * new matrix, and BOTH VECTORS ARE ZERO -- x and y of the old matrix do not carry over, spmv_hip_get_y directly
+ * after an upload returns zeros, and a run before spmv_hip_set_x leaves y zero.  spmv_hip_last_run_ns is
+ * SPMV_HIP_ERR_STATE until the next run (the event pair belonged to the old matrix), block X must be set again,
+ * and the stream of spmv_hip_set_stream and the context's flags stay as they are.
+ *
+ * An upload that is refused leaves the context in one of two states, never in between:
+ *   (a) as it was: the previous matrix, x and y are untouched and the next run continues from them;
+ *   (b) without a matrix: spmv_hip_ctx_info [0] is 0 and run / set_x / set_y / get_y are SPMV_HIP_ERR_STATE until
+ *       an upload succeeds.
+ * The uploads of the family headers (spmv_hip_upload_csr_symmetric, _transposed, _f32values, _compact,
+ * _compact_f64, _compact_f32xy) check all of their arguments on the host first: every refusal is (a).  For the
+ * four uploads below:
+ *   (a) a null pointer, a negative size, row_ptr[0] != 0, row_ptr[rows] != nnz, an ELLPACK size that overflows
+ *       int32, bad hybrid COO arguments -- what is seen before the device is touched;
+ *   (b) a decreasing row_ptr and any row or column index out of range (the indices are checked where they then
+ *       are, on the device, after the old matrix was freed), and any allocation or HIP failure on the way.
+ * A context of spmv_hip_create_multi: (a) for the argument checks and for the family uploads it refuses with
+ * SPMV_HIP_ERR_STATE, (b) for everything found once the rows are being dealt to the devices. */
+
 /* Copy a CSR matrix to the device and build its launch plan.
  * Takes what csr_matrix::Matrix holds (src/matrix/csr-matrix.hpp:58-64):
  * row_ptr[rows+1], column_index[row_ptr[rows]], value[row_ptr[rows]].

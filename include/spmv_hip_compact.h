@@ -80,7 +80,8 @@ void spmv_hip_c16_plan_destroy(spmv_hip_c16_plan *plan);
  * plan has no wide tile, NO 32-bit columns either: spmv_hip_ctx_info [9] then shows 6 bytes per stored entry plus row_ptr,
  * the vectors and the plan.  spmv_hip_ctx_info [15] reports spmv_hip_c16_plan_info [19], [6] its workgroups.  Refusals and
  * the SPMV_HIP_FLAG_EXACT_ORDER handling are those of spmv_hip_upload_csr_f32values; a context of spmv_hip_create_multi and
- * the block runs on a context that holds this upload are SPMV_HIP_ERR_STATE. */
+ * the block runs on a context that holds this upload are SPMV_HIP_ERR_STATE.  A refused upload leaves the previous matrix
+ * usable. */
 int spmv_hip_upload_csr_compact(spmv_hip_ctx *ctx, int32_t rows, int32_t cols, int32_t nnz, const int32_t *row_ptr,
                                 const int32_t *column_index, const double *value, int allow_rounding);
 

@@ -80,6 +80,8 @@ void spmv_hip_f32_plan_destroy(spmv_hip_f32_plan *plan);
  *   values that (float) changes while allow_rounding == 0: SPMV_HIP_ERR_INVALID, and spmv_hip_last_error names their count and
  *   the first offending entry;  a finite value whose float is infinite: SPMV_HIP_ERR_OVERFLOW;
  *   a context of spmv_hip_create_multi: SPMV_HIP_ERR_STATE.
+ * Everything is checked on the host before anything is freed: a refused upload leaves the previous matrix usable (spmv_hip.h,
+ * "uploads").
  * spmv_hip_set_block_x / spmv_hip_run_block ... on a context that holds this upload: SPMV_HIP_ERR_STATE (there are no fp64
  * values for them to read). */
 int spmv_hip_upload_csr_f32values(spmv_hip_ctx *ctx, int32_t rows, int32_t cols, int32_t nnz, const int32_t *row_ptr,

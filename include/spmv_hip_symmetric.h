@@ -42,7 +42,9 @@ int spmv_hip_csr_triangle(int32_t rows, const int32_t *host_row_ptr, const int32
  * set_y / last_run_ns / flush_caches behave as for any upload (x and y both have `rows` entries).  Refused:
  *   a matrix that spans both triangles, an unknown kind, a skew-symmetric one with a diagonal entry: SPMV_HIP_ERR_INVALID;
  *   a context of spmv_hip_create_multi: SPMV_HIP_ERR_STATE (a row partition would send transposed products across devices);
- *   a context created with SPMV_HIP_FLAG_EXACT_ORDER: SPMV_HIP_ERR_INVALID (that order cannot be kept). */
+ *   a context created with SPMV_HIP_FLAG_EXACT_ORDER: SPMV_HIP_ERR_INVALID (that order cannot be kept).
+ * A bad row_ptr, row_ptr[rows] != nnz and a column outside [0, rows) are SPMV_HIP_ERR_INVALID as well.  Everything is checked
+ * on the host before anything is freed: a refused upload leaves the previous matrix usable (spmv_hip.h, "uploads"). */
 int spmv_hip_upload_csr_symmetric(spmv_hip_ctx *ctx, int32_t rows, int32_t nnz, const int32_t *row_ptr,
                                   const int32_t *column_index, const double *value, int kind);
 

@@ -28,7 +28,9 @@ extern "C" {
  * run does nothing.  Refused:
  *   a null pointer, a negative size, a bad row_ptr, a column outside [0, cols): SPMV_HIP_ERR_INVALID;
  *   a context of spmv_hip_create_multi: SPMV_HIP_ERR_STATE (a row partition would need a reduction of y across devices);
- *   a context created with SPMV_HIP_FLAG_EXACT_ORDER: SPMV_HIP_ERR_INVALID (atomic adds keep no order). */
+ *   a context created with SPMV_HIP_FLAG_EXACT_ORDER: SPMV_HIP_ERR_INVALID (atomic adds keep no order).
+ * Everything is checked on the host before anything is freed: a refused upload leaves the previous matrix usable (spmv_hip.h,
+ * "uploads"). */
 int spmv_hip_upload_csr_transposed(spmv_hip_ctx *ctx, int32_t rows, int32_t cols, int32_t nnz, const int32_t *row_ptr,
                                    const int32_t *column_index, const double *value);
 

@@ -67,6 +67,7 @@ void free_ctx_matrix(spmv_hip_ctx * c)
     c->ell_as_tiles = false;
     c->as_csr = false;
     c->bytes = 0;
+    c->timed = false; // the event pair brackets a run of the matrix that is gone: spmv_hip_last_run_ns is ERR_STATE again
 }
 
 } // namespace spmvi

@@ -392,11 +392,18 @@ int spmv_hip_upload_csr_symmetric(spmv_hip_ctx * c, int32_t rows, int32_t nnz, c
     if (row_ptr[rows] != nnz)
         return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_ctx_matrix(c);
-    // the plan first: it refuses what is not a stored triangle before anything is copied
-    if ((rc = build_sym_plan(&c->sym_plan, rows, row_ptr, column_index, kind, 0, 0)) != 0)
+    // the plan first: it refuses what is not a stored triangle (a column out of range, an entry in the other triangle, an unknown
+    // kind) before anything is freed or copied, so that a refused upload leaves the previous matrix usable
+    spmv_hip_sym_plan * plan = nullptr;
+    if ((rc = build_sym_plan(&plan, rows, row_ptr, column_index, kind, 0, 0)) != 0)
         return rc;
+    const hipError_t idle = hipStreamSynchronize(c->stream);
+    if (idle != hipSuccess) {
+        spmv_hip_sym_plan_destroy(plan);
+        return fail_hip(idle, "hipStreamSynchronize");
+    }
+    free_ctx_matrix(c);
+    c->sym_plan = plan;
     if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) rows, (size_t) rows, (size_t) nnz, row_ptr, column_index, true, value, false)) != 0)
         return rc;
     c->rows = rows;

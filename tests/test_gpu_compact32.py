@@ -139,6 +139,23 @@ def _row_sums(rows, p, c, a32, x32):
     return oracle_py.Oracle().csr_spmv(rows, p, c, a32.astype(np.float64), x32.astype(np.float64), num_threads=1, runs=1)
 
 
+def restate(y, s):
+    """The restatement of one run: y <- float32(float64(y) + s)."""
+    return (y.astype(np.float64) + s).astype(np.float32)
+
+
+def one_run_bound(rows, p, c, a32, x32, y0, s):
+    """(t, bound) of the default order, one run: t = double(y0) + s before rounding; the sum of a row in another order is off by
+    at most delta_i (helpers.assert_close's a-priori bound on two summation orders), the rounding to float adds 2^-24 of what is
+    rounded, which is at most |t| + delta_i, and 2^-149 covers a result in the denormals."""
+    t = y0.astype(np.float64) + s
+    longest = int(np.max(np.diff(p))) if rows else 0
+    nterms = max(4096, longest)
+    scale = (helpers.abs_products(rows, p, c, a32.astype(np.float64), x32.astype(np.float64)) if rows and len(c) else np.zeros(rows)) + np.abs(y0.astype(np.float64))
+    delta = 2.0 * nterms * 2.0 ** -53 * scale
+    return t, 2.0 ** -24 * np.abs(t) + delta * (1.0 + 2.0 ** -24) + 2.0 ** -149
+
+
 def _check(name):
     rows, cols, p, c, v = cc.matrix(name)
     a32, x32, y0 = _uniform_inputs(name, rows, cols, v)
@@ -146,16 +163,8 @@ def _check(name):
     # the restatement: y <- float32(float64(y) + s), once per run
     want = y0.copy()
     for _ in range(RUNS):
-        want = (want.astype(np.float64) + s).astype(np.float32)
-    # default order, one run: t = double(y0) + s before rounding; the sum of a row in another order is off by at most delta_i
-    # (helpers.assert_close's a-priori bound on two summation orders), the rounding to float adds 2^-24 of what is rounded,
-    # which is at most |t| + delta_i, and 2^-149 covers a result in the denormals
-    t = y0.astype(np.float64) + s
-    longest = int(np.max(np.diff(p))) if rows else 0
-    nterms = max(4096, longest)
-    scale = (helpers.abs_products(rows, p, c, a32.astype(np.float64), x32.astype(np.float64)) if rows and len(c) else np.zeros(rows)) + np.abs(y0.astype(np.float64))
-    delta = 2.0 * nterms * 2.0 ** -53 * scale
-    bound = 2.0 ** -24 * np.abs(t) + delta * (1.0 + 2.0 ** -24) + 2.0 ** -149
+        want = restate(want, s)
+    t, bound = one_run_bound(rows, p, c, a32, x32, y0, s)
     dev = Device(rows, cols, p, c, a32, x32, y0)
     info = None
     for flags, order in ((0, "default order"), (capi.FLAG_EXACT_ORDER, "exact order")):

@@ -1,4 +1,6 @@
-"""Y += A X for k vectors (include/spmv_hip_multivec.h) on the MI355X.  For every matrix and k in 1, 2, 3, 4, 5, 6, 8 and 16:
+"""Y += A X for k vectors (include/spmv_hip_multivec.h) on the MI355X.  For every matrix and k in 1, 2, 3, 4, 5, 6, 8 and 16 -- and
+for every other k up to 16 (7 and 9 ... 15: the splits into three passes, 13 = 8 + 4 + 1 and 15 = 8 + 6 + 1, among them) on
+rect_wide and lengths_1_to_9000:
 
   * every column against the oracle (the CPU CSR loop) over three accumulating runs from a random Y, within the project's
     tolerance -- and bit for bit with SPMV_HIP_FLAG_EXACT_ORDER;
@@ -21,6 +23,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 RUNS = 3
 KS = [1, 2, 3, 4, 5, 6, 8, 16]
+KS_MORE = [7, 9, 10, 11, 12, 13, 14, 15]  # the remaining k, on MORE_ON only
+MORE_ON = ("rect_wide", "lengths_1_to_9000")
+WIDTHS = (8, 6, 4, 3, 2, 1)  # the compiled widths of a pass
 THREADS = min(16, os.cpu_count() or 1)
 
 
@@ -86,6 +91,16 @@ MATRICES = {
 def _matrix(name):
     rows, cols, p, c, v = MATRICES[name]()
     return rows, cols, np.ascontiguousarray(p, dtype=np.int32), np.ascontiguousarray(c, dtype=np.int32), np.ascontiguousarray(v, dtype=np.float64)
+
+
+def _passes(k):
+    """The greedy split of k over the compiled widths: the widest that still fits, until nothing is left."""
+    out = []
+    while k > 0:
+        w = next(w for w in WIDTHS if w <= k)
+        out.append(w)
+        k -= w
+    return out
 
 
 def _inputs(rows, cols, k, seed=5):
@@ -159,8 +174,7 @@ def _bits(a, b, what):
     helpers.assert_bitexact(np.ascontiguousarray(a).ravel(), np.ascontiguousarray(b).ravel(), what)
 
 
-@pytest.mark.parametrize("k", KS)
-@pytest.mark.parametrize("name", list(MATRICES))
+@pytest.mark.parametrize("name,k", [(name, k) for name in MATRICES for k in KS] + [(name, k) for name in MORE_ON for k in KS_MORE])
 def test_multivec(oracle, name, k):
     rows, cols, p, c, v = _matrix(name)
     X, Y0 = _inputs(rows, cols, k)
@@ -169,7 +183,7 @@ def test_multivec(oracle, name, k):
     scale = _scale(rows, cols, p, c, v, X, Y0)
     with capi.MvPlan(rows, cols, p, k, 0, D.stream) as plan, capi.MvPlan(rows, cols, p, 1, 0, D.stream) as one:
         info = plan.info()
-        assert info["k"] == k and info["rows"] == rows and info["passes"] == (1 if k in (1, 2, 3, 4, 6, 8) else 2)
+        assert info["k"] == k and info["rows"] == rows and info["passes"] == len(_passes(k)) and info["widest_pass"] == _passes(k)[0]
         lens = np.diff(p)
         assert info["long_rows"] == int((lens > 4096).sum())
         Y = D.spmm(plan, X, Y0)
