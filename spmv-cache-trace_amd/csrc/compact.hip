@@ -224,7 +224,7 @@ int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
 // and the same refusals apply; without one it is y += A x.
 template <class V, class T>
 int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const V * d_value,
-                 const T * d_x, T * d_y, void * stream, const ScaledArgs<T> * scale = nullptr)
+                 const T * d_x, T * d_y, void * stream, const ScaledArgs<T> * scale = nullptr, const DotsArgs * dots = nullptr)
 {
     if (!pl)
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
@@ -232,11 +232,20 @@ int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const 
         return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (scale) {
-        const int rc = scaled_vectors_check(pl->rows, sizeof(T), scale->beta, scale->y_in, d_y);
-        if (rc != 0 || pl->rows == 0)
+        int rc = scaled_vectors_check(pl->rows, sizeof(T), scale->beta, scale->y_in, d_y);
+        if (rc == 0 && dots)
+            rc = dots_check(*dots, pl->ntiles, pl->rows, pl->cols, pl->nnz, sizeof(T), sizeof(V), d_row_ptr, d_column_index, d_value, d_x,
+                            scale->beta, scale->y_in, d_y);
+        if (rc != 0)
             return rc;
-        if (scale->alpha == 0.0 || pl->ntiles == 0) // the beta part alone: neither the matrix nor x is read
+        if (pl->rows == 0)
+            return dots ? dots_reduce(*dots, 0, s) : SPMV_HIP_OK;
+        if (scale->alpha == 0.0 || pl->ntiles == 0) { // the beta part alone: neither the matrix nor x is read
+            if (dots)
+                return scaled_rows_only_dots(pl->rows, std::is_same<T, float>::value, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in,
+                                             d_y, *dots, s);
             return scaled_rows_only(pl->rows, std::is_same<T, float>::value, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, s);
+        }
     }
     if (pl->ntiles == 0) // rows, cols or nnz of zero
         return SPMV_HIP_OK;
@@ -252,6 +261,23 @@ int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const 
     const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
     const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
     const bool x32 = (long long) pl->cols * (long long) sizeof(T) < (1LL << 32);
+    if (dots) { // (x32 holds: dots_check)
+        const bool beta0 = scale->beta == 0.0, hasw = dots->w != nullptr;
+        void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, double, double,
+                       const T *, T *, const T *, spmv::v2d *, int);
+#define SPMV_C16_PICK(NAME) (beta0 ? (hasw ? spmv::NAME<true, true> : spmv::NAME<true, false>) : (hasw ? spmv::NAME<false, true> : spmv::NAME<false, false>))
+        if constexpr (std::is_same<T, float>::value)
+            kernel = SPMV_C16_PICK(csr_compact_f32xy_scaled_dots_kernel);
+        else if constexpr (std::is_same<V, float>::value)
+            kernel = SPMV_C16_PICK(csr_compact_scaled_dots_kernel);
+        else
+            kernel = SPMV_C16_PICK(csr_compact_f64_scaled_dots_kernel);
+#undef SPMV_C16_PICK
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
+                           scale->alpha, scale->beta, scale->y_in, d_y, static_cast<const T *>(dots->w), static_cast<spmv::v2d *>(dots->work), exact);
+        HIP_TRY(hipGetLastError());
+        return dots_reduce(*dots, pl->ntiles, s);
+    }
     if (scale) {
         const bool beta0 = scale->beta == 0.0;
         void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, double, double,
@@ -418,6 +444,41 @@ int spmv_hip_csr_spmv_c16_f32xy_scaled(const spmv_hip_c16_plan * pl, const int32
 {
     const ScaledArgs<float> scale{alpha, beta, d_y_in};
     return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale);
+}
+
+int spmv_hip_c16_dots_workspace(const spmv_hip_c16_plan * pl, size_t * bytes)
+{
+    if (!pl || !bytes)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null, or bytes");
+    *bytes = dots_workspace_bytes(pl->ntiles, pl->rows);
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_csr_spmv_c16_scaled_dots(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                                      const double * d_x, double alpha, double beta, const double * d_y_in, double * d_y_out, const double * d_w,
+                                      double * d_dots, void * d_work, size_t work_bytes, void * stream)
+{
+    const ScaledArgs<double> scale{alpha, beta, d_y_in};
+    const DotsArgs dots{d_w, d_dots, d_work, work_bytes};
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale, &dots);
+}
+
+int spmv_hip_csr_spmv_c16_f64_scaled_dots(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
+                                          const double * d_value, const double * d_x, double alpha, double beta, const double * d_y_in,
+                                          double * d_y_out, const double * d_w, double * d_dots, void * d_work, size_t work_bytes, void * stream)
+{
+    const ScaledArgs<double> scale{alpha, beta, d_y_in};
+    const DotsArgs dots{d_w, d_dots, d_work, work_bytes};
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale, &dots);
+}
+
+int spmv_hip_csr_spmv_c16_f32xy_scaled_dots(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
+                                            const float * d_value, const float * d_x, double alpha, double beta, const float * d_y_in,
+                                            float * d_y_out, const float * d_w, double * d_dots, void * d_work, size_t work_bytes, void * stream)
+{
+    const ScaledArgs<float> scale{alpha, beta, d_y_in};
+    const DotsArgs dots{d_w, d_dots, d_work, work_bytes};
+    return c16_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale, &dots);
 }
 
 int spmv_hip_c16_plan_verify(const spmv_hip_c16_plan * pl, const int32_t * d_column_index, int64_t * mismatches, void * stream)

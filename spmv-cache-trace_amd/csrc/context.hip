@@ -40,6 +40,10 @@ void free_ctx_matrix(spmv_hip_ctx * c)
     if (c->d_x32) (void) hipFree(c->d_x32);
     if (c->d_y32) (void) hipFree(c->d_y32);
     c->d_x32 = c->d_y32 = nullptr;
+    if (c->d_dots) (void) hipFree(c->d_dots);
+    c->d_dots = nullptr;
+    c->dots_work_bytes = 0;
+    c->dots_run = false;
     if (c->mv_plan) {
         spmv_hip_mv_plan_destroy(c->mv_plan);
         c->mv_plan = nullptr;
@@ -835,6 +839,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
         return fail(SPMV_HIP_ERR_STATE, "no matrix uploaded");
     if (c->multi)
         return multi_run(c);
+    c->dots_run = false;
     HIP_TRY(hipSetDevice(c->device));
     const bool timed = !(c->flags & SPMV_HIP_FLAG_NO_RUN_EVENTS);
     if (timed)
@@ -890,28 +895,52 @@ int spmv_hip_run(spmv_hip_ctx * c)
     return SPMV_HIP_OK;
 }
 
-// spmv_hip_scaled.h: the context's y <- alpha A x + beta y, in place, for the four float-tile formats
-int spmv_hip_run_scaled(spmv_hip_ctx * c, double alpha, double beta)
+// spmv_hip_scaled.h: the context's y <- alpha A x + beta y, in place, for the four float-tile formats; with_dots:
+// spmv_hip_dots.h's spmv_hip_run_scaled_dots (`what` names the entry point in a refusal)
+static int run_scaled(spmv_hip_ctx * c, double alpha, double beta, bool with_dots, const char * what)
 {
     if (!c)
         return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
     if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "spmv_hip_run_scaled runs on one device (a context of spmv_hip_create), on formats 7 to 10");
+        return fail(SPMV_HIP_ERR_STATE, (std::string(what) + " runs on one device (a context of spmv_hip_create), on formats 7 to 10").c_str());
     if (c->format < 7 || c->format > 10) {
         const std::string text = (c->format == 0 ? std::string("no matrix uploaded (format 0)") : "the context holds format " + std::to_string(c->format)) +
-            ": spmv_hip_run_scaled needs format 7 (fp32 values), 8, 9 or 10 (compact)";
+            ": " + what + " needs format 7 (fp32 values), 8, 9 or 10 (compact)";
         return fail(SPMV_HIP_ERR_STATE, text.c_str());
     }
     HIP_TRY(hipSetDevice(c->device));
+    c->dots_run = false;
+    if (with_dots && !c->d_dots) { // the dots in front of the workspace
+        size_t bytes = 0;
+        const int rc = c->format == 7 ? spmv_hip_f32_dots_workspace(c->f32_plan, &bytes) : spmv_hip_c16_dots_workspace(c->c16_plan, &bytes);
+        if (rc != 0)
+            return rc;
+        HIP_TRY(hipMalloc((void **) &c->d_dots, 16 + bytes));
+        c->dots_work_bytes = bytes;
+        c->bytes += 16 + bytes;
+    }
     const bool timed = !(c->flags & SPMV_HIP_FLAG_NO_RUN_EVENTS);
     if (timed)
         HIP_TRY(hipEventRecord(c->ev0, c->stream));
     int rc = SPMV_HIP_OK;
-    switch (c->format) {
-    case 7: rc = spmv_hip_csr_spmv_f32_scaled(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
-    case 8: rc = spmv_hip_csr_spmv_c16_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
-    case 9: rc = spmv_hip_csr_spmv_c16_f64_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
-    default: rc = spmv_hip_csr_spmv_c16_f32xy_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, alpha, beta, c->d_y32, c->d_y32, c->stream); break;
+    if (with_dots) {
+        const bool square = c->rows == c->cols;
+        double * dots = c->d_dots;
+        void * work = c->d_dots + 2;
+        const size_t wb = c->dots_work_bytes;
+        switch (c->format) {
+        case 7: rc = spmv_hip_csr_spmv_f32_scaled_dots(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, square ? c->d_x : nullptr, dots, work, wb, c->stream); break;
+        case 8: rc = spmv_hip_csr_spmv_c16_scaled_dots(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, square ? c->d_x : nullptr, dots, work, wb, c->stream); break;
+        case 9: rc = spmv_hip_csr_spmv_c16_f64_scaled_dots(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, alpha, beta, c->d_y, c->d_y, square ? c->d_x : nullptr, dots, work, wb, c->stream); break;
+        default: rc = spmv_hip_csr_spmv_c16_f32xy_scaled_dots(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, alpha, beta, c->d_y32, c->d_y32, square ? c->d_x32 : nullptr, dots, work, wb, c->stream); break;
+        }
+    } else {
+        switch (c->format) {
+        case 7: rc = spmv_hip_csr_spmv_f32_scaled(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
+        case 8: rc = spmv_hip_csr_spmv_c16_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
+        case 9: rc = spmv_hip_csr_spmv_c16_f64_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
+        default: rc = spmv_hip_csr_spmv_c16_f32xy_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, alpha, beta, c->d_y32, c->d_y32, c->stream); break;
+        }
     }
     if (rc != 0)
         return rc;
@@ -919,6 +948,29 @@ int spmv_hip_run_scaled(spmv_hip_ctx * c, double alpha, double beta)
         HIP_TRY(hipEventRecord(c->ev1, c->stream));
         c->timed = true;
     }
+    c->dots_run = with_dots;
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_run_scaled(spmv_hip_ctx * c, double alpha, double beta)
+{
+    return run_scaled(c, alpha, beta, false, "spmv_hip_run_scaled");
+}
+
+int spmv_hip_run_scaled_dots(spmv_hip_ctx * c, double alpha, double beta)
+{
+    return run_scaled(c, alpha, beta, true, "spmv_hip_run_scaled_dots");
+}
+
+int spmv_hip_get_dots(spmv_hip_ctx * c, double dots[2])
+{
+    if (!c || !dots)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null, or dots");
+    if (c->multi || !c->dots_run || !c->d_dots)
+        return fail(SPMV_HIP_ERR_STATE, "the last run on this matrix was not spmv_hip_run_scaled_dots");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(dots, c->d_dots, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SPMV_HIP_OK;
 }
 

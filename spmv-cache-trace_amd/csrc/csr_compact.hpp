@@ -15,7 +15,7 @@
 // and a row's sum is rounded once where it is stored; the products and the LDS slice are doubles as everywhere.
 #pragma once
 
-#include "csr_f32values.hpp"
+#include "csr_dots.hpp"
 
 namespace spmv {
 
@@ -153,6 +153,28 @@ SPMV_C16_SCALED_KERNEL(csr_compact_scaled_kernel, float, double)
 SPMV_C16_SCALED_KERNEL(csr_compact_f64_scaled_kernel, double, double)
 SPMV_C16_SCALED_KERNEL(csr_compact_f32xy_scaled_kernel, float, float)
 #undef SPMV_C16_SCALED_KERNEL
+
+// ---- ... and with the two dots of y_out (include/spmv_hip_dots.h): the epilogue of csr_dots.hpp, then the wave's pair into its
+// tile's slot.  compact_wave returns where the wave has no tile; such a wave has no slot either.  HASW: d_w is not null.
+#define SPMV_C16_DOTS_KERNEL(NAME, V, T)                                                                                                    \
+    template <bool BETA0, bool HASW>                                                                                                       \
+    __global__ __launch_bounds__(256, 8) void NAME(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,            \
+                                                   const uint16_t * __restrict__ codes, const int32_t * __restrict__ p,                    \
+                                                   const int32_t * __restrict__ j, const V * __restrict__ a, const T * __restrict__ x,     \
+                                                   double alpha, double beta, const T * y_in, T * y_out, const T * dw,                     \
+                                                   v2d * __restrict__ slots, int exact_order)                                              \
+    {                                                                                                                                      \
+        double sums[2] = {0.0, 0.0};                                                                                                       \
+        compact_wave<true>(ntiles, desc, bases, codes, p, j, a, x, ScaledDotRows<T, BETA0, HASW>{alpha, beta, y_in, y_out, dw, sums},      \
+                           exact_order);                                                                                                   \
+        const int w = (int) blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);                                      \
+        if (w < ntiles)                                                                                                                    \
+            store_wave_dots(slots, w, sums);                                                                                               \
+    }
+SPMV_C16_DOTS_KERNEL(csr_compact_scaled_dots_kernel, float, double)
+SPMV_C16_DOTS_KERNEL(csr_compact_f64_scaled_dots_kernel, double, double)
+SPMV_C16_DOTS_KERNEL(csr_compact_f32xy_scaled_dots_kernel, float, float)
+#undef SPMV_C16_DOTS_KERNEL
 
 // spmv_hip_c16_plan_verify: a wave per tile; every entry of a compact tile decoded and compared with the caller's column
 static __global__ __launch_bounds__(256) void c16_verify_kernel(int ntiles, const int4 * __restrict__ desc, const int * __restrict__ bases,

@@ -51,4 +51,27 @@ int scaled_vectors_check(int32_t rows, size_t elem, double beta, const void * y_
 // the call where no tile runs (alpha == 0, or a plan without tiles: zterm says that alpha * +0.0 is still added): one vector kernel
 int scaled_rows_only(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out, hipStream_t s);
 
+// ---- ... with the two dots of y_out (include/spmv_hip_dots.h) ----------------------------------------------------------------------
+
+// the dots of one call: w (null: no second dot), where the two doubles go, and the caller's workspace
+struct DotsArgs {
+    const void * w;
+    double * dots;
+    void * work;
+    size_t work_bytes;
+};
+
+// Workspace of a plan with `ntiles` tiles over `rows` rows: one 16-byte slot per tile or, where no tile runs, per 64 rows, then
+// one per workgroup of the reduction's first stage; at least 16 bytes.
+size_t dots_workspace_bytes(int ntiles, int32_t rows);
+// What only a call with dots refuses, after scaled_vectors_check has passed: the list of spmv_hip_dots.h.  elem is sizeof(T),
+// value_elem the size of a stored value; null arrays are not compared.
+int dots_check(const DotsArgs & d, int ntiles, int32_t rows, int32_t cols, int32_t nnz, size_t elem, size_t value_elem, const void * row_ptr,
+               const void * column_index, const void * value, const void * x, double beta, const void * y_in, const void * y_out);
+// dots <- the sum of the first n slots of the workspace, in one or two launches on s (n == 0: +0.0, +0.0)
+int dots_reduce(const DotsArgs & d, int n, hipStream_t s);
+// scaled_rows_only with the dots of what it stores
+int scaled_rows_only_dots(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out,
+                          const DotsArgs & d, hipStream_t s);
+
 } // namespace spmvi

@@ -2,7 +2,7 @@
 // cuts the rows into wave tiles on the host from row_ptr alone (the plain tiles of plan_csr.hip: lanes per row from the tile's
 // longest row, at most 16 entries per lane); the kernel is csr_f32values.hpp.
 #include "f32_plan.hpp"
-#include "csr_f32values.hpp"
+#include "csr_dots.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -65,9 +65,10 @@ int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_er
     return SPMV_HIP_OK;
 }
 
-// spmv_hip_csr_spmv_f32 (scale null: y += fl32(A) x) and spmv_hip_csr_spmv_f32_scaled (d_y is y_out): one set of refusals
+// spmv_hip_csr_spmv_f32 (scale null: y += fl32(A) x), spmv_hip_csr_spmv_f32_scaled (d_y is y_out) and, with dots,
+// spmv_hip_csr_spmv_f32_scaled_dots: one set of refusals
 int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
-                 const double * d_x, double * d_y, void * stream, const ScaledArgs<double> * scale)
+                 const double * d_x, double * d_y, void * stream, const ScaledArgs<double> * scale, const DotsArgs * dots = nullptr)
 {
     if (!pl)
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
@@ -75,11 +76,19 @@ int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const 
         return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (scale) {
-        const int rc = scaled_vectors_check(pl->rows, sizeof(double), scale->beta, scale->y_in, d_y);
-        if (rc != 0 || pl->rows == 0)
+        int rc = scaled_vectors_check(pl->rows, sizeof(double), scale->beta, scale->y_in, d_y);
+        if (rc == 0 && dots)
+            rc = dots_check(*dots, pl->ntiles, pl->rows, pl->cols, pl->nnz, sizeof(double), sizeof(float), d_row_ptr, d_column_index, d_value, d_x,
+                            scale->beta, scale->y_in, d_y);
+        if (rc != 0)
             return rc;
-        if (scale->alpha == 0.0 || pl->ntiles == 0) // the beta part alone: neither the matrix nor x is read
+        if (pl->rows == 0)
+            return dots ? dots_reduce(*dots, 0, s) : SPMV_HIP_OK;
+        if (scale->alpha == 0.0 || pl->ntiles == 0) { // the beta part alone: neither the matrix nor x is read
+            if (dots)
+                return scaled_rows_only_dots(pl->rows, false, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, *dots, s);
             return scaled_rows_only(pl->rows, false, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, s);
+        }
     }
     if (pl->ntiles == 0) // rows, cols or nnz of zero
         return SPMV_HIP_OK;
@@ -90,6 +99,19 @@ int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const 
     const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
     const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
     const bool x32 = (long long) pl->cols * 8 < (1LL << 32);
+    if (dots) { // (x32 holds: dots_check)
+        const bool beta0 = scale->beta == 0.0, hasw = dots->w != nullptr;
+        void (*kernel)(int, const int4 *, const int32_t *, const int32_t *, const float *, const double *, double, double, const double *, double *,
+                       const double *, spmv::v2d *, int);
+        if (beta0)
+            kernel = hasw ? spmv::csr_f32values_scaled_dots_kernel<true, true> : spmv::csr_f32values_scaled_dots_kernel<true, false>;
+        else
+            kernel = hasw ? spmv::csr_f32values_scaled_dots_kernel<false, true> : spmv::csr_f32values_scaled_dots_kernel<false, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, scale->alpha, scale->beta,
+                           scale->y_in, d_y, static_cast<const double *>(dots->w), static_cast<spmv::v2d *>(dots->work), exact);
+        HIP_TRY(hipGetLastError());
+        return dots_reduce(*dots, pl->ntiles, s);
+    }
     if (scale) {
         void (*kernel)(int, const int4 *, const int32_t *, const int32_t *, const float *, const double *, double, double, const double *, double *, int);
         if (scale->beta == 0.0)
@@ -117,6 +139,35 @@ int rows_only(int32_t rows, bool zterm, double alpha, double beta, const T * y_i
     hipLaunchKernelGGL(kernel, dim3((unsigned) (((long long) rows + 255) / 256)), dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out);
     HIP_TRY(hipGetLastError());
     return SPMV_HIP_OK;
+}
+
+// slots of the path without tiles (one per wave of scaled_rows_only_dots_kernel), and workgroups of the reduction's first stage
+long long row_slots(int32_t rows) { return ((long long) rows + 63) / 64; }
+long long reduce_blocks(long long n) { return (n + spmv::kDotsChunk - 1) / spmv::kDotsChunk; }
+
+template <class T>
+int rows_only_dots(int32_t rows, bool zterm, double alpha, double beta, const T * y_in, T * y_out, const DotsArgs & d, hipStream_t s)
+{
+    void (*kernel)(int, double, double, const T *, T *, const T *, spmv::v2d *);
+    const bool beta0 = beta == 0.0, hasw = d.w != nullptr;
+#define SPMV_ROWS_PICK(B, Z) (hasw ? spmv::scaled_rows_only_dots_kernel<T, B, Z, true> : spmv::scaled_rows_only_dots_kernel<T, B, Z, false>)
+    if (beta0)
+        kernel = zterm ? SPMV_ROWS_PICK(true, true) : SPMV_ROWS_PICK(true, false);
+    else
+        kernel = zterm ? SPMV_ROWS_PICK(false, true) : SPMV_ROWS_PICK(false, false);
+#undef SPMV_ROWS_PICK
+    hipLaunchKernelGGL(kernel, dim3((unsigned) (((long long) rows + 255) / 256)), dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out,
+                       static_cast<const T *>(d.w), static_cast<spmv::v2d *>(d.work));
+    HIP_TRY(hipGetLastError());
+    return dots_reduce(d, (int) row_slots(rows), s);
+}
+
+bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned long long bbytes)
+{
+    if (!a || !b || abytes == 0 || bbytes == 0)
+        return false;
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return p < q + bbytes && q < p + abytes;
 }
 
 } // namespace
@@ -251,9 +302,89 @@ int scaled_rows_only(int32_t rows, bool float_vectors, bool zterm, double alpha,
     return rows_only(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), s);
 }
 
+int scaled_rows_only_dots(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out,
+                          const DotsArgs & d, hipStream_t s)
+{
+    if (float_vectors)
+        return rows_only_dots(rows, zterm, alpha, beta, static_cast<const float *>(y_in), static_cast<float *>(y_out), d, s);
+    return rows_only_dots(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), d, s);
+}
+
+size_t dots_workspace_bytes(int ntiles, int32_t rows)
+{
+    const long long slots = std::max<long long>(ntiles, row_slots(rows));
+    return (size_t) std::max<long long>(16, 16 * (slots + reduce_blocks(slots)));
+}
+
+int dots_check(const DotsArgs & d, int ntiles, int32_t rows, int32_t cols, int32_t nnz, size_t elem, size_t value_elem, const void * row_ptr,
+               const void * column_index, const void * value, const void * x, double beta, const void * y_in, const void * y_out)
+{
+    if (!d.dots || !d.work)
+        return fail(SPMV_HIP_ERR_INVALID, "d_dots or d_work is null");
+    const size_t need = dots_workspace_bytes(ntiles, rows);
+    if (d.work_bytes < need) {
+        char text[160];
+        std::snprintf(text, sizeof text, "work_bytes is %zu and the plan needs %zu (spmv_hip_*_dots_workspace)", d.work_bytes, need);
+        return fail(SPMV_HIP_ERR_INVALID, text);
+    }
+    if (!aligned16(d.dots) || !aligned16(d.work))
+        return fail(SPMV_HIP_ERR_ALIGN, "d_dots and d_work must be 16-byte aligned");
+    if (elem == 4 && (reinterpret_cast<uintptr_t>(d.w) & 3u))
+        return fail(SPMV_HIP_ERR_ALIGN, "d_w must be 4-byte aligned");
+    if ((unsigned long long) cols * elem >= (1ULL << 32))
+        return fail(SPMV_HIP_ERR_INVALID, "x spans 4 GiB or more: the multiplies with dots have no kernel for such vectors");
+    const unsigned long long vec = (unsigned long long) rows * elem;
+    if (overlap(d.w, vec, y_out, vec))
+        return fail(SPMV_HIP_ERR_INVALID, "d_w overlaps d_y_out");
+    if (overlap(d.dots, 16, d.work, need))
+        return fail(SPMV_HIP_ERR_INVALID, "d_dots and d_work overlap");
+    const struct {
+        const void * p;
+        unsigned long long bytes;
+    } arrays[] = {{row_ptr, 4ULL * ((unsigned long long) rows + 1)}, {column_index, 4ULL * (unsigned long long) nnz},
+                  {value, (unsigned long long) value_elem * (unsigned long long) nnz}, {x, (unsigned long long) cols * elem},
+                  {beta != 0.0 ? y_in : nullptr, vec}, {y_out, vec}, {d.w, vec}};
+    for (auto const & a : arrays)
+        if (overlap(d.dots, 16, a.p, a.bytes) || overlap(d.work, need, a.p, a.bytes))
+            return fail(SPMV_HIP_ERR_INVALID, "d_dots or d_work overlaps an array of the call");
+    return SPMV_HIP_OK;
+}
+
+int dots_reduce(const DotsArgs & d, int n, hipStream_t s)
+{
+    spmv::v2d * slots = static_cast<spmv::v2d *>(d.work);
+    spmv::v2d * out = reinterpret_cast<spmv::v2d *>(d.dots);
+    const long long blocks = reduce_blocks(n);
+    if (blocks > 1) { // two stages: a partial sum per chunk of slots behind the slots, then their sum
+        hipLaunchKernelGGL(spmv::dots_reduce_kernel<256>, dim3((unsigned) blocks), dim3(256), 0, s, n, spmv::kDotsChunk, slots, slots + n);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(spmv::dots_reduce_kernel<256>, dim3(1), dim3(256), 0, s, (int) blocks, (int) blocks, slots + n, out);
+    } else
+        hipLaunchKernelGGL(spmv::dots_reduce_kernel<256>, dim3(1), dim3(256), 0, s, n, spmv::kDotsChunk, slots, out);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
 } // namespace spmvi
 
 extern "C" {
+
+int spmv_hip_f32_dots_workspace(const spmv_hip_f32_plan * pl, size_t * bytes)
+{
+    if (!pl || !bytes)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null, or bytes");
+    *bytes = dots_workspace_bytes(pl->ntiles, pl->rows);
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_csr_spmv_f32_scaled_dots(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
+                                      const float * d_value, const double * d_x, double alpha, double beta, const double * d_y_in,
+                                      double * d_y_out, const double * d_w, double * d_dots, void * d_work, size_t work_bytes, void * stream)
+{
+    const ScaledArgs<double> scale{alpha, beta, d_y_in};
+    const DotsArgs dots{d_w, d_dots, d_work, work_bytes};
+    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale, &dots);
+}
 
 int spmv_hip_narrow_values_host(int64_t n, const double * value, float * out, int64_t * inexact, double * max_rel_err)
 {

@@ -25,6 +25,7 @@
 #include "spmv_hip_compact_f64.h"
 #include "spmv_hip_compact_f32xy.h"
 #include "spmv_hip_scaled.h"
+#include "spmv_hip_dots.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only: librccl.so is dlopen'ed by spmv_hip_create_multi when G > 1
@@ -230,6 +231,11 @@ struct spmv_hip_ctx {
     float * d_val32 = nullptr;              // ... its values
     spmv_hip_c16_plan * c16_plan = nullptr; // formats 8 and 10 (compact.hip; their values are d_val32 too) and 9 (... d_val)
     float *d_x32 = nullptr, *d_y32 = nullptr; // format 10: the vectors
+    // spmv_hip_run_scaled_dots (formats 7 to 10; spmv_hip_dots.h): the two dots, then the workspace, in one allocation made by the
+    // first such run after an upload; dots_run: the last run on this matrix was one (what spmv_hip_get_dots asks for)
+    double * d_dots = nullptr;
+    size_t dots_work_bytes = 0;
+    bool dots_run = false;
     // block vectors of spmv_hip_run_block (multivec.hip; format 1 only): X (cols x block_k) and Y (rows x block_k), row-major,
     // apart from d_x / d_y; the plan is made on the first run_block after the matrix or k changed
     spmv_hip_mv_plan * mv_plan = nullptr;

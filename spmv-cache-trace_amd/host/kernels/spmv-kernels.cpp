@@ -13,9 +13,11 @@
 #include "spmv_hip_compact_f64.h"
 #include "spmv_hip_compact_f32xy.h"
 #include "spmv_hip_scaled.h"
+#include "spmv_hip_dots.h"
 #include "spmv_hip_tuning.h" // (spmv_hip.h + the CSR algorithm choice and ctx_info of the CLI)
 
 #include <chrono>
+#include <cmath>
 #include <ostream>
 #include <sstream>
 #include <system_error>
@@ -363,11 +365,15 @@ public:
     void run(TraceConfig const &) override
     {
         if (is_master()) {
-            if (options.scaled) // --alpha / --beta (the float-tile kernels only: main.cpp refuses them elsewhere)
+            if (options.dots) // --dots (with --alpha / --beta only: main.cpp)
+                check(spmv_hip_run_scaled_dots(ctx, options.alpha, options.beta), "run_scaled_dots");
+            else if (options.scaled) // --alpha / --beta (the float-tile kernels only: main.cpp refuses them elsewhere)
                 check(spmv_hip_run_scaled(ctx, options.alpha, options.beta), "run_scaled");
             else
                 check(spmv_hip_run(ctx), "run");
             check(spmv_hip_sync(ctx), "sync");
+            if (options.dots)
+                check(spmv_hip_get_dots(ctx, dots), "get_dots");
             std::uint64_t ns = 0, gns = 0;
             if (spmv_hip_last_run_times(ctx, &ns, &gns) == SPMV_HIP_OK) {
                 device_ns = ns;
@@ -378,6 +384,14 @@ public:
 
     MemoryReferenceString memory_reference_string(TraceConfig const &, int, int) const override { no_reference_string(); }
     std::uint64_t last_device_ns() const override { return device_ns; }
+    bool last_dots(double * out) const override
+    {
+        if (!options.dots)
+            return false;
+        out[0] = dots[0];
+        out[1] = dots[1];
+        return true;
+    }
     void flush_caches() override { check(spmv_hip_flush_caches(ctx), "flush_caches"); }
 
     std::vector<double> result() const override
@@ -424,6 +438,16 @@ protected:
             std::ostringstream t;
             t.precision(17);
             t << ",\n\"alpha\": " << options.alpha << ",\n\"beta\": " << options.beta;
+            if (options.dots) { // --dots: {y' y, x' y} of the last run (a string where JSON has no number for it)
+                t << ",\n\"dots\": [";
+                for (int k = 0; k < 2; ++k) {
+                    if (std::isfinite(dots[k]))
+                        t << dots[k];
+                    else
+                        t << '"' << dots[k] << '"';
+                    t << (k == 0 ? ", " : "]");
+                }
+            }
             o << t.str();
         }
         return o;
@@ -463,6 +487,7 @@ protected:
     spmv_hip_ctx * ctx = nullptr;
     aligned_vector<double> x, y;
     std::uint64_t device_ns = 0, gather_ns = 0;
+    double dots[2] = {0.0, 0.0}; // --dots: of the last run
     double init_load_seconds = 0.0, init_upload_seconds = 0.0; // wall time of Kernel::init: file -> host arrays -> device + plan
     std::string prepare_error;
 };

@@ -54,6 +54,8 @@ struct SpmvOptions
                                    // (--f32-values=exact): hip-csr, one device (spmv_hip_upload_csr_f32values, spmv_hip_f32values.h)
     bool scaled = false;           // EXTENSION: --alpha / --beta were given: every run is y <- alpha A x + beta y (spmv_hip_run_scaled,
     double alpha = 1.0, beta = 1.0; // spmv_hip_scaled.h), with --f32-values or --compact only
+    bool dots = false;             // EXTENSION: --dots, with --alpha / --beta: every run also leaves y' y and x' y of the new y on the device
+                                   // (spmv_hip_run_scaled_dots, spmv_hip_dots.h)
     int compact = 0;               // EXTENSION: --f32-values (1 = round, 2 = exact) with the columns of a tile as 16-bit window codes
                                    // (--compact[=round|exact]): hip-csr, one device (spmv_hip_upload_csr_compact, spmv_hip_compact.h)
                                    // 3 = f64 (--compact=f64): the fp64 values as they are beside the codes (spmv_hip_upload_csr_compact_f64)

@@ -100,6 +100,7 @@ enum Key
     key_compact,
     key_alpha,
     key_beta,
+    key_dots,
 };
 
 bool parse_count(char const * arg, long long & out)
@@ -234,9 +235,15 @@ error_t parse_option(int key, char * arg, argp_state * state)
         a.spmv.scaled = true;
         break;
     }
+    case key_dots:
+        a.spmv.dots = true;
+        break;
     case ARGP_KEY_END:
         if (a.list_perf_events)
             break;
+        if (a.spmv.dots && (!a.spmv.scaled || (!a.spmv.f32_values && !a.spmv.compact)))
+            argp_error(state, "--dots needs --alpha / --beta and --f32-values or --compact[=f64|f32]: the dots are those of the scaled "
+                              "multiplies over float tiles (spmv_hip_run_scaled_dots)");
         if (a.spmv.scaled && !a.spmv.f32_values && !a.spmv.compact)
             argp_error(state, "--alpha / --beta need --f32-values or --compact[=f64|f32]: only the multiplies over float tiles have a scaled "
                               "form, y <- alpha A x + beta y (spmv_hip_run_scaled)");
@@ -358,6 +365,40 @@ double relative_error(std::vector<double> const & y, std::vector<double> const &
     return scale > 0.0 ? err / scale : err;
 }
 
+// The exactly rounded sum of finite doubles (Shewchuk's growing expansion of non-overlapping partials): what --dots --check
+// restates the device's dots against.  Anything non-finite gives the plain sum.
+double exact_sum(std::vector<double> const & t)
+{
+    std::vector<double> partials;
+    for (double x : t) {
+        if (!std::isfinite(x)) {
+            double plain = 0.0;
+            for (double const e : t)
+                plain += e;
+            return plain;
+        }
+        std::size_t kept = 0;
+        for (double y : partials) {
+            if (std::fabs(x) < std::fabs(y))
+                std::swap(x, y);
+            volatile double const hi = x + y;
+            volatile double const back = hi - x;
+            double const lo = y - back;
+            if (lo != 0.0)
+                partials[kept++] = lo;
+            x = hi;
+        }
+        partials.resize(kept);
+        partials.push_back(x);
+    }
+    // the partials do not overlap and grow in magnitude: adding them from the largest down rounds once where the rest is below
+    // half an ulp, which holds for all but a tie; the tie is within one ulp of a sum whose bound is rows times wider
+    double sum = 0.0;
+    for (std::size_t k = partials.size(); k-- > 0;)
+        sum += partials[k];
+    return sum;
+}
+
 // x_i = uniform(-1, 1) from a hash of i: a check with x = 1 only compares row sums
 std::vector<double> uniform_x(std::size_t n)
 {
@@ -438,6 +479,10 @@ int main(int argc, char ** argv)
          "one launch (spmv_hip_run_scaled); A and B default to 1, and the JSON document names both.  --check compares with the CPU "
          "CSR kernel's product put through the same number of scaled steps on the host", 2},
         {"beta", key_beta, "B", 0, "EXTENSION: see --alpha", 2},
+        {"dots", key_dots, 0, 0,
+         "EXTENSION (with --alpha / --beta): every run also computes y' y and x' y of the y it has just written, in the same launch "
+         "(spmv_hip_run_scaled_dots; x' y only where the matrix is square, otherwise 0); the JSON document names those of the last run "
+         "as \"dots\".  --check restates both on the host from the y it reads back, within rows 2^-53 sum |products|", 2},
         {"vectors", key_vectors, "K", 0,
          "EXTENSION (hip-csr, one device): Y += A X for K = 1 ... 16 vectors in one multiply, every stored entry read once; column c "
          "of X is x scaled by c + 1.  Flops count 2 nnz K; --check compares every column with the CPU CSR kernel", 2},
@@ -678,6 +723,41 @@ int main(int argc, char ** argv)
             else
                 std::snprintf(buf, sizeof buf, "%.3e", err);
             parity += buf;
+            bool dots_pass = true;
+            std::string dots_report;
+            double device_dots[2];
+            if (kernel->last_dots(device_dots)) {
+                // --dots: both restated from the y read back, t_i the rounded products and their exactly rounded sum; any order of
+                // adding them in fp64 stays within rows 2^-53 sum |t_i| of it.  x is what the device holds (all ones, or --x uniform; floats
+                // under --compact=f32), and only a square matrix has an x' y
+                std::size_t const n = got.size();
+                bool const square = n == kernel->columns();
+                std::vector<double> t[2] = {std::vector<double>(n), std::vector<double>(n, 0.0)};
+                for (std::size_t i = 0; i < n; ++i) {
+                    double xi = xv.empty() ? 1.0 : (i < xv.size() ? xv[i] : 0.0);
+                    if (float_vectors)
+                        xi = static_cast<double>(static_cast<float>(xi));
+                    volatile double const yy = got[i] * got[i], xy = square ? xi * got[i] : 0.0;
+                    t[0][i] = yy;
+                    t[1][i] = xy;
+                }
+                dots_report = ", \"dots\": {\"restated\": [";
+                std::string bounds;
+                for (int d = 0; d < 2; ++d) {
+                    double const want = exact_sum(t[d]);
+                    double mag = 0.0;
+                    for (double const e : t[d])
+                        mag += std::fabs(e);
+                    double const bound = (double) n * std::ldexp(1.0, -53) * mag;
+                    if (!(std::fabs(device_dots[d] - want) <= bound)) // (false for NaN)
+                        dots_pass = false;
+                    std::snprintf(buf, sizeof buf, std::isfinite(want) ? "%.17g" : "\"%g\"", want);
+                    dots_report += std::string(buf) + (d == 0 ? ", " : "]");
+                    std::snprintf(buf, sizeof buf, std::isfinite(bound) ? "%.3e" : "\"%g\"", bound);
+                    bounds += std::string(buf) + (d == 0 ? ", " : "]");
+                }
+                dots_report += ", \"bound\": [" + bounds + ", \"pass\": " + (dots_pass ? "true" : "false") + "}";
+            }
             // --compact=f32: run k rounds a y of magnitude about k s once, so after R runs the roundings sum to at most
             // 2^-24 s R (R + 1) / 2 against a result of R s: (R + 1) 2^-25, and the fp64 additions' share in the factor beside it
             double tolerance = 1e-10;
@@ -685,7 +765,7 @@ int main(int argc, char ** argv)
                 tolerance += (args.profile + 2.0) * std::ldexp(1.0, -25) * (1.0 + std::ldexp(1.0, -10));
             std::snprintf(buf, sizeof buf, "%.6e", tolerance);
             // err <= tolerance is false for NaN: non-finite values and size mismatches fail
-            parity += std::string(", \"tolerance\": ") + (float_vectors ? buf : "1e-10") + ", \"pass\": " + (err <= tolerance ? "true" : "false") + "}";
+            parity += std::string(", \"tolerance\": ") + (float_vectors ? buf : "1e-10") + ", \"pass\": " + (err <= tolerance ? "true" : "false") + dots_report + "}";
         }
 
         profiling.set_extra(parity);

@@ -1,6 +1,6 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
-spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h and
-spmv_hip_scaled.h (the C ABI of libspmv_hip.so).
+spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
+spmv_hip_scaled.h and spmv_hip_dots.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -25,7 +25,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
-                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h")]
+                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -158,6 +158,14 @@ SIGNATURES = {
     "spmv_hip_csr_spmv_c16_f64_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     "spmv_hip_csr_spmv_c16_f32xy_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     "spmv_hip_run_scaled": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "spmv_hip_f32_dots_workspace": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "spmv_hip_c16_dots_workspace": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "spmv_hip_csr_spmv_f32_scaled_dots": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_csr_spmv_c16_scaled_dots": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_csr_spmv_c16_f64_scaled_dots": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_csr_spmv_c16_f32xy_scaled_dots": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_run_scaled_dots": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "spmv_hip_get_dots": (C.c_int, [_vp, _vp]),
 }
 
 
@@ -424,6 +432,19 @@ class Context:
             check(self.lib.spmv_hip_run_scaled(self.h, alpha, beta))
         if sync:
             check(self.lib.spmv_hip_sync(self.h))
+
+    def run_scaled_dots(self, alpha, beta, runs=1, sync=True):
+        """run_scaled, and the dots {y' y, x' y} of the new y on the device (include/spmv_hip_dots.h): get_dots reads them."""
+        for _ in range(runs):
+            check(self.lib.spmv_hip_run_scaled_dots(self.h, alpha, beta))
+        if sync:
+            check(self.lib.spmv_hip_sync(self.h))
+
+    def get_dots(self):
+        """The two dots of the last run_scaled_dots (waits for the stream); x' y is +0.0 where rows != cols."""
+        d = np.zeros(2)
+        check(self.lib.spmv_hip_get_dots(self.h, d.ctypes.data))
+        return d
 
     def set_block_x(self, X):
         """X: (cols, k) host array, 1 <= k <= 16 (include/spmv_hip_multivec.h); a new k starts a new X / Y pair (Y zero)."""
@@ -750,6 +771,18 @@ class F32Plan:
         check(self.lib.spmv_hip_csr_spmv_f32_scaled(self.h, d_row_ptr or None, d_col or None, d_val32 or None, d_x or None, alpha, beta,
                                                     d_y_in or None, d_y_out or None, stream))
 
+    def dots_workspace_bytes(self):
+        """The workspace a spmv_scaled_dots call through this plan needs (include/spmv_hip_dots.h)."""
+        n = C.c_size_t(0)
+        check(self.lib.spmv_hip_f32_dots_workspace(self.h, C.byref(n)))
+        return n.value
+
+    def spmv_scaled_dots(self, d_row_ptr, d_col, d_val32, d_x, alpha, beta, d_y_in, d_y_out, d_w, d_dots, d_work, work_bytes, stream=0):
+        """spmv_scaled, and d_dots <- {y_out' y_out, w' y_out} (two doubles on the device; d_w may be 0 / None: +0.0)."""
+        check(self.lib.spmv_hip_csr_spmv_f32_scaled_dots(self.h, d_row_ptr or None, d_col or None, d_val32 or None, d_x or None, alpha, beta,
+                                                         d_y_in or None, d_y_out or None, d_w or None, d_dots or None, d_work or None,
+                                                         work_bytes, stream))
+
 
 C16_INFO_KEYS = ["rows", "cols", "stored_entries", "flags", "workgroups", "tiles", "compact_tiles", "wide_tiles", "long_row_tiles",
                  "compact_entries"] + ["tiles_with_%d_windows" % w for w in range(1, 9)] + ["device_bytes", "streamed_bytes"]
@@ -848,6 +881,32 @@ class C16Plan:
         """y_out <- fl32(alpha fl32(A) x + beta y_in) on float vectors through the same plan, otherwise as spmv_scaled."""
         check(self.lib.spmv_hip_csr_spmv_c16_f32xy_scaled(self.h, d_row_ptr or None, d_col or None, d_val32 or None, d_x32 or None, alpha, beta,
                                                           d_y_in32 or None, d_y_out32 or None, stream))
+
+    def dots_workspace_bytes(self):
+        """The workspace a *_scaled_dots call through this plan needs (include/spmv_hip_dots.h)."""
+        n = C.c_size_t(0)
+        check(self.lib.spmv_hip_c16_dots_workspace(self.h, C.byref(n)))
+        return n.value
+
+    def _dots(self, fn, d_row_ptr, d_col, d_val, d_x, alpha, beta, d_y_in, d_y_out, d_w, d_dots, d_work, work_bytes, stream):
+        check(fn(self.h, d_row_ptr or None, d_col or None, d_val or None, d_x or None, alpha, beta, d_y_in or None, d_y_out or None,
+                 d_w or None, d_dots or None, d_work or None, work_bytes, stream))
+
+    def spmv_scaled_dots(self, d_row_ptr, d_col, d_val32, d_x, alpha, beta, d_y_in, d_y_out, d_w, d_dots, d_work, work_bytes, stream=0):
+        """spmv_scaled, and d_dots <- {y_out' y_out, w' y_out} (two doubles on the device; d_w may be 0 / None: +0.0)."""
+        self._dots(self.lib.spmv_hip_csr_spmv_c16_scaled_dots, d_row_ptr, d_col, d_val32, d_x, alpha, beta, d_y_in, d_y_out, d_w, d_dots,
+                   d_work, work_bytes, stream)
+
+    def spmv_f64_scaled_dots(self, d_row_ptr, d_col, d_val, d_x, alpha, beta, d_y_in, d_y_out, d_w, d_dots, d_work, work_bytes, stream=0):
+        """spmv_f64_scaled, and the dots."""
+        self._dots(self.lib.spmv_hip_csr_spmv_c16_f64_scaled_dots, d_row_ptr, d_col, d_val, d_x, alpha, beta, d_y_in, d_y_out, d_w, d_dots,
+                   d_work, work_bytes, stream)
+
+    def spmv_f32xy_scaled_dots(self, d_row_ptr, d_col, d_val32, d_x32, alpha, beta, d_y_in32, d_y_out32, d_w32, d_dots, d_work, work_bytes,
+                               stream=0):
+        """spmv_f32xy_scaled, and the dots of the floats it stored (d_w32 a float array)."""
+        self._dots(self.lib.spmv_hip_csr_spmv_c16_f32xy_scaled_dots, d_row_ptr, d_col, d_val32, d_x32, alpha, beta, d_y_in32, d_y_out32, d_w32,
+                   d_dots, d_work, work_bytes, stream)
 
     def verify(self, d_col, stream=0):
         """How many entries of compact tiles decode to a column other than d_col's (the content guard)."""
