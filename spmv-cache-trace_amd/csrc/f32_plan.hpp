@@ -61,6 +61,8 @@ struct DotsArgs {
     size_t work_bytes;
 };
 
+// do [a, a + abytes) and [b, b + bbytes) share a byte?  A null or empty array overlaps nothing.
+bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned long long bbytes);
 // Workspace of a plan with `ntiles` tiles over `rows` rows: one 16-byte slot per tile or, where no tile runs, per 64 rows, then
 // one per workgroup of the reduction's first stage; at least 16 bytes.
 size_t dots_workspace_bytes(int ntiles, int32_t rows);

@@ -162,6 +162,12 @@ int rows_only_dots(int32_t rows, bool zterm, double alpha, double beta, const T 
     return dots_reduce(d, (int) row_slots(rows), s);
 }
 
+} // namespace
+
+// ---- what compact.hip and krylov.hip share (f32_plan.hpp) ------------------------------------------------------------------------------------
+
+namespace spmvi {
+
 bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned long long bbytes)
 {
     if (!a || !b || abytes == 0 || bbytes == 0)
@@ -169,12 +175,6 @@ bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned
     const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
     return p < q + bbytes && q < p + abytes;
 }
-
-} // namespace
-
-// ---- what compact.hip shares (f32_plan.hpp) ------------------------------------------------------------------------------------
-
-namespace spmvi {
 
 int f32_check_host(int32_t rows, int32_t cols, const int32_t * rp, unsigned flags)
 {

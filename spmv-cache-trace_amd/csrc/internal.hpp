@@ -12,6 +12,7 @@
 //   transpose.hip    y += A' x from the CSR arrays of A as they are (spmv_hip_transpose.h)
 //   f32values.hip    y += fl32(A) x with the values stored as 4-byte floats (spmv_hip_f32values.h)
 //   compact.hip      ... and the columns of a tile as 16-bit window codes (spmv_hip_compact.h)
+//   krylov.hip       the vector updates of a CG iteration with their scalars read from device memory (spmv_hip_krylov.h)
 // The last two share one tiling rule and the narrowing of the values (f32_plan.hpp, defined in f32values.hip) and one tile
 // kernel body over three column sources (csr_f32values.hpp: f32_tile; csr_compact.hpp adds the two code sources).
 #pragma once

@@ -1,0 +1,143 @@
+// krylov.hip -- include/spmv_hip_krylov.h: the step and the direction of a conjugate-gradient iteration over caller-owned device
+// vectors, their scalar a quotient of two doubles in device memory.  The kernels are cg_updates.hpp; the reduction of the step's
+// slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).
+#include "spmv_hip_krylov.h"
+
+#include "f32_plan.hpp"
+#include "cg_updates.hpp"
+
+#include <cstdio>
+
+using namespace spmvi;
+
+namespace {
+
+static_assert(spmv::kKrylovChunk == SPMV_HIP_KRYLOV_CHUNK, "the header documents the chunk");
+
+long long krylov_slots(long long n) { return (n + spmv::kKrylovChunk - 1) / spmv::kKrylovChunk; }
+
+// one slot per chunk, then one per workgroup of the reduction's first stage
+size_t krylov_bytes(long long n) { return dots_workspace_bytes((int) krylov_slots(n), 0); }
+
+struct Array {
+    const void * p;
+    unsigned long long bytes;
+    bool written;
+    int align;
+    const char * name;
+};
+
+// what both calls refuse, in the order of spmv_hip_dots.h: null, (the workspace's size: the caller), alignment, 4 GiB, overlaps
+int check_arrays(int32_t n, size_t elem, const Array * arrays, int count)
+{
+    char text[160];
+    for (int i = 0; i < count; ++i)
+        if ((reinterpret_cast<uintptr_t>(arrays[i].p) & (uintptr_t) (arrays[i].align - 1)) != 0) {
+            std::snprintf(text, sizeof text, "%s must be %d-byte aligned", arrays[i].name, arrays[i].align);
+            return fail(SPMV_HIP_ERR_ALIGN, text);
+        }
+    if ((unsigned long long) n * elem >= (1ULL << 32))
+        return fail(SPMV_HIP_ERR_INVALID, "the vectors span 4 GiB or more: the updates have no kernel for such vectors");
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if ((arrays[i].written || arrays[j].written) && overlap(arrays[i].p, arrays[i].bytes, arrays[j].p, arrays[j].bytes)) {
+                std::snprintf(text, sizeof text, "%s and %s overlap, and one of them is written", arrays[i].name, arrays[j].name);
+                return fail(SPMV_HIP_ERR_INVALID, text);
+            }
+    return SPMV_HIP_OK;
+}
+
+template <class T>
+int cg_step(int32_t n, const double * d_num, const double * d_den, const T * d_p, const T * d_q, T * d_x, T * d_r, const T * d_minv, double * d_dots,
+            void * d_work, size_t work_bytes, void * stream)
+{
+    if (n < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "n < 0");
+    if (!d_num || !d_den || !d_p || !d_q || !d_x || !d_r || !d_dots || !d_work)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_minv may be null)");
+    const size_t need = krylov_bytes(n);
+    if (work_bytes < need) {
+        char text[160];
+        std::snprintf(text, sizeof text, "work_bytes is %zu and n needs %zu (spmv_hip_krylov_workspace)", work_bytes, need);
+        return fail(SPMV_HIP_ERR_INVALID, text);
+    }
+    const unsigned long long vec = (unsigned long long) n * sizeof(T);
+    const Array arrays[] = {{d_p, vec, false, 16, "d_p"},       {d_q, vec, false, 16, "d_q"},       {d_x, vec, true, 16, "d_x"},
+                            {d_r, vec, true, 16, "d_r"},        {d_minv, vec, false, 16, "d_minv"}, {d_dots, 16, true, 16, "d_dots"},
+                            {d_work, need, true, 16, "d_work"}, {d_num, 8, false, 8, "d_num"},      {d_den, 8, false, 8, "d_den"}};
+    const int rc = check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    if (rc != 0)
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long slots = krylov_slots(n);
+    if (slots > 0) {
+        void (*kernel)(long long, const double *, const double *, const T *, const T *, T *, T *, const T *, spmv::v2d *) =
+            d_minv ? spmv::cg_step_kernel<T, true> : spmv::cg_step_kernel<T, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, s, (long long) n, d_num, d_den, d_p, d_q, d_x, d_r, d_minv,
+                           static_cast<spmv::v2d *>(d_work));
+        HIP_TRY(hipGetLastError());
+    }
+    return dots_reduce(DotsArgs{nullptr, d_dots, d_work, work_bytes}, (int) slots, s);
+}
+
+template <class T>
+int cg_direction(int32_t n, const double * d_num, const double * d_den, const T * d_r, const T * d_minv, T * d_p, void * stream)
+{
+    if (n < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "n < 0");
+    if (!d_num || !d_den || !d_r || !d_p)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_minv may be null)");
+    const unsigned long long vec = (unsigned long long) n * sizeof(T);
+    const Array arrays[] = {{d_r, vec, false, 16, "d_r"}, {d_minv, vec, false, 16, "d_minv"}, {d_p, vec, true, 16, "d_p"},
+                            {d_num, 8, false, 8, "d_num"}, {d_den, 8, false, 8, "d_den"}};
+    const int rc = check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    if (rc != 0)
+        return rc;
+    const long long slots = krylov_slots(n);
+    if (slots == 0)
+        return SPMV_HIP_OK;
+    void (*kernel)(long long, const double *, const double *, const T *, const T *, T *) =
+        d_minv ? spmv::cg_direction_kernel<T, true> : spmv::cg_direction_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), (long long) n, d_num, d_den, d_r,
+                       d_minv, d_p);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int spmv_hip_krylov_workspace(int32_t n, size_t * bytes)
+{
+    if (n < 0 || !bytes)
+        return fail(SPMV_HIP_ERR_INVALID, "n < 0, or bytes is null");
+    *bytes = krylov_bytes(n);
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_cg_step_f64(int32_t n, const double * d_num, const double * d_den, const double * d_p, const double * d_q, double * d_x, double * d_r,
+                         const double * d_minv, double * d_dots, void * d_work, size_t work_bytes, void * stream)
+{
+    return cg_step(n, d_num, d_den, d_p, d_q, d_x, d_r, d_minv, d_dots, d_work, work_bytes, stream);
+}
+
+int spmv_hip_cg_step_f32(int32_t n, const double * d_num, const double * d_den, const float * d_p, const float * d_q, float * d_x, float * d_r,
+                         const float * d_minv, double * d_dots, void * d_work, size_t work_bytes, void * stream)
+{
+    return cg_step(n, d_num, d_den, d_p, d_q, d_x, d_r, d_minv, d_dots, d_work, work_bytes, stream);
+}
+
+int spmv_hip_cg_direction_f64(int32_t n, const double * d_num, const double * d_den, const double * d_r, const double * d_minv, double * d_p,
+                              void * stream)
+{
+    return cg_direction(n, d_num, d_den, d_r, d_minv, d_p, stream);
+}
+
+int spmv_hip_cg_direction_f32(int32_t n, const double * d_num, const double * d_den, const float * d_r, const float * d_minv, float * d_p,
+                              void * stream)
+{
+    return cg_direction(n, d_num, d_den, d_r, d_minv, d_p, stream);
+}
+
+} // extern "C"

@@ -1,6 +1,6 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
-spmv_hip_scaled.h and spmv_hip_dots.h (the C ABI of libspmv_hip.so).
+spmv_hip_scaled.h, spmv_hip_dots.h and spmv_hip_krylov.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -25,7 +25,8 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_ROOT), "include", "spmv_hip.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include", n)
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
-                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h")]
+                                          "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
+                                          "spmv_hip_krylov.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -166,6 +167,12 @@ SIGNATURES = {
     "spmv_hip_csr_spmv_c16_f32xy_scaled_dots": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "spmv_hip_run_scaled_dots": (C.c_int, [_vp, C.c_double, C.c_double]),
     "spmv_hip_get_dots": (C.c_int, [_vp, _vp]),
+    # spmv_hip_krylov.h
+    "spmv_hip_krylov_workspace": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "spmv_hip_cg_step_f64": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_cg_step_f32": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_cg_direction_f64": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_cg_direction_f32": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -930,6 +937,45 @@ def _dev(a):
             return a.data_ptr(), a.stride(0)
         return a.data_ptr(), None
     return int(a), None
+
+
+def krylov_workspace_bytes(n):
+    """The workspace a cg_step over n elements needs (include/spmv_hip_krylov.h): a function of n alone, at least 16."""
+    b = C.c_size_t(0)
+    check(load().spmv_hip_krylov_workspace(n, C.byref(b)))
+    return b.value
+
+
+def _krylov_suffix(vectors, dtype):
+    """"f64" or "f32": the dtype of the torch tensors among the vectors (one dtype), or `dtype` where all are raw addresses."""
+    found = {str(v.dtype).split(".")[-1] for v in vectors if hasattr(v, "data_ptr")}
+    if dtype is not None:
+        found.add(np.dtype(dtype).name)
+    if len(found) != 1 or not found <= {"float64", "float32"}:
+        raise TypeError("the vectors are float64 or float32, all of one type (raw addresses: dtype=); got %s" % sorted(found))
+    return "f64" if found == {"float64"} else "f32"
+
+
+def _addr(a):
+    return None if a is None else (_dev(a)[0] or None)
+
+
+def cg_step(n, d_num, d_den, d_p, d_q, d_x, d_r, d_minv, d_dots, d_work, work_bytes=None, stream=0, dtype=None):
+    """x += a p, r -= a q in place with a = d_num[0] / d_den[0] read on the device, and d_dots <- {r' r, r' diag(d_minv) r} of the
+    new r (d_minv None: +0.0).  Torch tensors or raw device addresses; float64 or float32 vectors by their dtype (raw addresses:
+    dtype=), d_num, d_den and d_dots always doubles.  work_bytes defaults to the size of a tensor d_work.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_cg_step_" + _krylov_suffix((d_p, d_q, d_x, d_r, d_minv), dtype))
+    if work_bytes is None:
+        work_bytes = d_work.numel() * d_work.element_size()
+    check(fn(n, _addr(d_num), _addr(d_den), _addr(d_p), _addr(d_q), _addr(d_x), _addr(d_r), _addr(d_minv), _addr(d_dots), _addr(d_work),
+             work_bytes, stream))
+
+
+def cg_direction(n, d_num, d_den, d_r, d_minv, d_p, stream=0, dtype=None):
+    """p <- z + b p in place with b = d_num[0] / d_den[0] read on the device and z = diag(d_minv) r (d_minv None: z = r).
+    Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_cg_direction_" + _krylov_suffix((d_r, d_minv, d_p), dtype))
+    check(fn(n, _addr(d_num), _addr(d_den), _addr(d_r), _addr(d_minv), _addr(d_p), stream))
 
 
 class MvPlan:
