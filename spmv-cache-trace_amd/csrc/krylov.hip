@@ -1,34 +1,26 @@
 // krylov.hip -- include/spmv_hip_krylov.h: the step and the direction of a conjugate-gradient iteration over caller-owned device
 // vectors, their scalar a quotient of two doubles in device memory.  The kernels are cg_updates.hpp; the reduction of the step's
-// slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).
+// slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).  The workspace rule and the check of a call's arrays
+// are shared with bicgstab.hip (krylov_check.hpp).
 #include "spmv_hip_krylov.h"
 
-#include "f32_plan.hpp"
+#include "krylov_check.hpp"
 #include "cg_updates.hpp"
 
 #include <cstdio>
 
 using namespace spmvi;
 
-namespace {
-
 static_assert(spmv::kKrylovChunk == SPMV_HIP_KRYLOV_CHUNK, "the header documents the chunk");
+
+namespace spmvi {
 
 long long krylov_slots(long long n) { return (n + spmv::kKrylovChunk - 1) / spmv::kKrylovChunk; }
 
 // one slot per chunk, then one per workgroup of the reduction's first stage
 size_t krylov_bytes(long long n) { return dots_workspace_bytes((int) krylov_slots(n), 0); }
 
-struct Array {
-    const void * p;
-    unsigned long long bytes;
-    bool written;
-    int align;
-    const char * name;
-};
-
-// what both calls refuse, in the order of spmv_hip_dots.h: null, (the workspace's size: the caller), alignment, 4 GiB, overlaps
-int check_arrays(int32_t n, size_t elem, const Array * arrays, int count)
+int krylov_check_arrays(int32_t n, size_t elem, const KrylovArray * arrays, int count)
 {
     char text[160];
     for (int i = 0; i < count; ++i)
@@ -47,6 +39,10 @@ int check_arrays(int32_t n, size_t elem, const Array * arrays, int count)
     return SPMV_HIP_OK;
 }
 
+} // namespace spmvi
+
+namespace {
+
 template <class T>
 int cg_step(int32_t n, const double * d_num, const double * d_den, const T * d_p, const T * d_q, T * d_x, T * d_r, const T * d_minv, double * d_dots,
             void * d_work, size_t work_bytes, void * stream)
@@ -62,10 +58,10 @@ int cg_step(int32_t n, const double * d_num, const double * d_den, const T * d_p
         return fail(SPMV_HIP_ERR_INVALID, text);
     }
     const unsigned long long vec = (unsigned long long) n * sizeof(T);
-    const Array arrays[] = {{d_p, vec, false, 16, "d_p"},       {d_q, vec, false, 16, "d_q"},       {d_x, vec, true, 16, "d_x"},
-                            {d_r, vec, true, 16, "d_r"},        {d_minv, vec, false, 16, "d_minv"}, {d_dots, 16, true, 16, "d_dots"},
-                            {d_work, need, true, 16, "d_work"}, {d_num, 8, false, 8, "d_num"},      {d_den, 8, false, 8, "d_den"}};
-    const int rc = check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    const KrylovArray arrays[] = {{d_p, vec, false, 16, "d_p"},       {d_q, vec, false, 16, "d_q"},       {d_x, vec, true, 16, "d_x"},
+                                  {d_r, vec, true, 16, "d_r"},        {d_minv, vec, false, 16, "d_minv"}, {d_dots, 16, true, 16, "d_dots"},
+                                  {d_work, need, true, 16, "d_work"}, {d_num, 8, false, 8, "d_num"},      {d_den, 8, false, 8, "d_den"}};
+    const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -88,9 +84,9 @@ int cg_direction(int32_t n, const double * d_num, const double * d_den, const T 
     if (!d_num || !d_den || !d_r || !d_p)
         return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_minv may be null)");
     const unsigned long long vec = (unsigned long long) n * sizeof(T);
-    const Array arrays[] = {{d_r, vec, false, 16, "d_r"}, {d_minv, vec, false, 16, "d_minv"}, {d_p, vec, true, 16, "d_p"},
-                            {d_num, 8, false, 8, "d_num"}, {d_den, 8, false, 8, "d_den"}};
-    const int rc = check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    const KrylovArray arrays[] = {{d_r, vec, false, 16, "d_r"}, {d_minv, vec, false, 16, "d_minv"}, {d_p, vec, true, 16, "d_p"},
+                                  {d_num, 8, false, 8, "d_num"}, {d_den, 8, false, 8, "d_den"}};
+    const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
     const long long slots = krylov_slots(n);

@@ -1,6 +1,6 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
-spmv_hip_scaled.h, spmv_hip_dots.h and spmv_hip_krylov.h (the C ABI of libspmv_hip.so).
+spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h and spmv_hip_bicgstab.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -26,7 +26,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
-                                          "spmv_hip_krylov.h")]
+                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -173,6 +173,13 @@ SIGNATURES = {
     "spmv_hip_cg_step_f32": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "spmv_hip_cg_direction_f64": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_cg_direction_f32": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # spmv_hip_bicgstab.h
+    "spmv_hip_bicgstab_s_f64": (C.c_int, [C.c_int32] + [_vp] * 7),
+    "spmv_hip_bicgstab_s_f32": (C.c_int, [C.c_int32] + [_vp] * 7),
+    "spmv_hip_bicgstab_step_f64": (C.c_int, [C.c_int32] + [_vp] * 12 + [C.c_size_t, _vp]),
+    "spmv_hip_bicgstab_step_f32": (C.c_int, [C.c_int32] + [_vp] * 12 + [C.c_size_t, _vp]),
+    "spmv_hip_bicgstab_direction_f64": (C.c_int, [C.c_int32] + [_vp] * 12),
+    "spmv_hip_bicgstab_direction_f32": (C.c_int, [C.c_int32] + [_vp] * 12),
 }
 
 
@@ -976,6 +983,33 @@ def cg_direction(n, d_num, d_den, d_r, d_minv, d_p, stream=0, dtype=None):
     Arguments as for cg_step.  Only enqueues."""
     fn = getattr(load(), "spmv_hip_cg_direction_" + _krylov_suffix((d_r, d_minv, d_p), dtype))
     check(fn(n, _addr(d_num), _addr(d_den), _addr(d_r), _addr(d_minv), _addr(d_p), stream))
+
+
+def bicgstab_s(n, d_num, d_den, d_v, d_r, d_minv, d_shat, stream=0, dtype=None):
+    """r <- s = r - a v in place with a = d_num[0] / d_den[0] read on the device; with d_minv, d_shat <- diag(d_minv) s (both None
+    or both given) (include/spmv_hip_bicgstab.h).  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_bicgstab_s_" + _krylov_suffix((d_v, d_r, d_minv, d_shat), dtype))
+    check(fn(n, _addr(d_num), _addr(d_den), _addr(d_v), _addr(d_r), _addr(d_minv), _addr(d_shat), stream))
+
+
+def bicgstab_step(n, d_num_a, d_den_a, d_num_w, d_den_w, d_phat, d_shat, d_t, d_rhat, d_x, d_r, d_dots, d_work, work_bytes=None, stream=0,
+                  dtype=None):
+    """x += a phat + w shat, r <- r - w t in place (r holds s on entry; d_shat None: shat is that r) with a = d_num_a[0] / d_den_a[0]
+    and w = d_num_w[0] / d_den_w[0] read on the device, and d_dots <- {r' r, rhat' r} of the new r.  Arguments as for cg_step, the
+    workspace krylov_workspace_bytes(n).  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_bicgstab_step_" + _krylov_suffix((d_phat, d_shat, d_t, d_rhat, d_x, d_r), dtype))
+    if work_bytes is None:
+        work_bytes = d_work.numel() * d_work.element_size()
+    check(fn(n, _addr(d_num_a), _addr(d_den_a), _addr(d_num_w), _addr(d_den_w), _addr(d_phat), _addr(d_shat), _addr(d_t), _addr(d_rhat),
+             _addr(d_x), _addr(d_r), _addr(d_dots), _addr(d_work), work_bytes, stream))
+
+
+def bicgstab_direction(n, d_num_r, d_den_r, d_num_a, d_den_a, d_num_w, d_den_w, d_r, d_v, d_p, d_minv, d_phat, stream=0, dtype=None):
+    """p <- r + b (p - w v) in place with w = d_num_w[0] / d_den_w[0] and b = (d_num_r[0] / d_den_r[0]) ((d_num_a[0] / d_den_a[0]) / w)
+    read on the device; with d_minv, d_phat <- diag(d_minv) p (both None or both given).  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_bicgstab_direction_" + _krylov_suffix((d_r, d_v, d_p, d_minv, d_phat), dtype))
+    check(fn(n, _addr(d_num_r), _addr(d_den_r), _addr(d_num_a), _addr(d_den_a), _addr(d_num_w), _addr(d_den_w), _addr(d_r), _addr(d_v),
+             _addr(d_p), _addr(d_minv), _addr(d_phat), stream))
 
 
 class MvPlan:
