@@ -91,15 +91,15 @@ __global__ __launch_bounds__(256) void scaled_rows_only_dots_kernel(int rows, do
         store_wave_dots(slots, (int) (i >> 6), sums);
 }
 
-// out[b] = the sum of in[b * per_block, min(n, (b + 1) * per_block)): thread t adds the elements t, t + 256, ... in that order,
-// a butterfly per wave, and thread 0 adds the four waves left to right.  The order depends on n and per_block alone.  One
-// workgroup with per_block >= n is the whole sum (n == 0: +0.0, +0.0).
+// The sum of in[b * per_block, min(n, (b + 1) * per_block)) for workgroup b: thread t adds the elements t, t + 256, ... in that
+// order, a butterfly per wave, and thread 0 adds the four waves left to right and is the one thread that holds the result.  The
+// order depends on n and per_block alone.  One workgroup with per_block >= n is the whole sum (n == 0: +0.0, +0.0).
 template <int THREADS>
-__global__ __launch_bounds__(THREADS) void dots_reduce_kernel(int n, int per_block, const v2d * __restrict__ in, v2d * __restrict__ out)
+__device__ __forceinline__ v2d dots_reduce_block(int n, int per_block, const v2d * __restrict__ in, long long b)
 {
     static_assert(THREADS == 256, "four waves");
     __shared__ v2d part[THREADS / kWave];
-    const long long first = (long long) blockIdx.x * per_block;
+    const long long first = b * per_block;
     const long long rest = (long long) n - first;
     const int count = (int) (rest < per_block ? rest : per_block);
     const v2d * src = in + first;
@@ -109,18 +109,28 @@ __global__ __launch_bounds__(THREADS) void dots_reduce_kernel(int n, int per_blo
         sums[0] += s.x;
         sums[1] += s.y;
     }
-    const double a = group_sum<kWave>(sums[0]), b = group_sum<kWave>(sums[1]);
+    const double a = group_sum<kWave>(sums[0]), c = group_sum<kWave>(sums[1]);
     if (((int) threadIdx.x & (kWave - 1)) == 0)
-        part[threadIdx.x >> 6] = v2d{a, b};
+        part[threadIdx.x >> 6] = v2d{a, c};
     __syncthreads();
+    v2d total = v2d{0.0, 0.0};
     if (threadIdx.x == 0) {
-        v2d total = part[0];
+        total = part[0];
         for (int q = 1; q < THREADS / kWave; ++q) {
             total.x += part[q].x;
             total.y += part[q].y;
         }
-        out[blockIdx.x] = total;
     }
+    return total;
+}
+
+// out[b] = dots_reduce_block of workgroup b
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void dots_reduce_kernel(int n, int per_block, const v2d * __restrict__ in, v2d * __restrict__ out)
+{
+    const v2d total = dots_reduce_block<THREADS>(n, per_block, in, (long long) blockIdx.x);
+    if (threadIdx.x == 0)
+        out[blockIdx.x] = total;
 }
 
 } // namespace spmv

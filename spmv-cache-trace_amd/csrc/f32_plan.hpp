@@ -70,6 +70,8 @@ size_t dots_workspace_bytes(int ntiles, int32_t rows);
 // value_elem the size of a stored value; null arrays are not compared.
 int dots_check(const DotsArgs & d, int ntiles, int32_t rows, int32_t cols, int32_t nnz, size_t elem, size_t value_elem, const void * row_ptr,
                const void * column_index, const void * value, const void * x, double beta, const void * y_in, const void * y_out);
+// the workgroups of the reduction's first stage over n slots (one: a single stage): dots_reduce's rule, for gmres.hip to share
+long long reduce_blocks(long long n);
 // dots <- the sum of the first n slots of the workspace, in one or two launches on s (n == 0: +0.0, +0.0)
 int dots_reduce(const DotsArgs & d, int n, hipStream_t s);
 // scaled_rows_only with the dots of what it stores

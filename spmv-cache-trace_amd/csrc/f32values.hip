@@ -141,9 +141,8 @@ int rows_only(int32_t rows, bool zterm, double alpha, double beta, const T * y_i
     return SPMV_HIP_OK;
 }
 
-// slots of the path without tiles (one per wave of scaled_rows_only_dots_kernel), and workgroups of the reduction's first stage
+// slots of the path without tiles (one per wave of scaled_rows_only_dots_kernel)
 long long row_slots(int32_t rows) { return ((long long) rows + 63) / 64; }
-long long reduce_blocks(long long n) { return (n + spmv::kDotsChunk - 1) / spmv::kDotsChunk; }
 
 template <class T>
 int rows_only_dots(int32_t rows, bool zterm, double alpha, double beta, const T * y_in, T * y_out, const DotsArgs & d, hipStream_t s)
@@ -167,6 +166,8 @@ int rows_only_dots(int32_t rows, bool zterm, double alpha, double beta, const T 
 // ---- what compact.hip and krylov.hip share (f32_plan.hpp) ------------------------------------------------------------------------------------
 
 namespace spmvi {
+
+long long reduce_blocks(long long n) { return (n + spmv::kDotsChunk - 1) / spmv::kDotsChunk; }
 
 bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned long long bbytes)
 {

@@ -1,6 +1,6 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
-spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h and spmv_hip_bicgstab.h (the C ABI of libspmv_hip.so).
+spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h and spmv_hip_gmres.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -26,7 +26,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
-                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h")]
+                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -180,6 +180,20 @@ SIGNATURES = {
     "spmv_hip_bicgstab_step_f32": (C.c_int, [C.c_int32] + [_vp] * 12 + [C.c_size_t, _vp]),
     "spmv_hip_bicgstab_direction_f64": (C.c_int, [C.c_int32] + [_vp] * 12),
     "spmv_hip_bicgstab_direction_f32": (C.c_int, [C.c_int32] + [_vp] * 12),
+    # spmv_hip_gmres.h
+    "spmv_hip_gmres_workspace": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "spmv_hip_gmres_state_doubles": (C.c_int, [C.c_int32]),
+    "spmv_hip_gmres_project_f64": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_gmres_project_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_gmres_update_f64": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_gmres_update_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_gmres_scale_f64": (C.c_int, [C.c_int32] + [_vp] * 5),
+    "spmv_hip_gmres_scale_f32": (C.c_int, [C.c_int32] + [_vp] * 5),
+    "spmv_hip_gmres_correct_f64": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    "spmv_hip_gmres_correct_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    "spmv_hip_gmres_start": (C.c_int, [C.c_int32, _vp, _vp, _vp]),
+    "spmv_hip_gmres_column": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_hip_gmres_solve": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp]),
 }
 
 
@@ -1010,6 +1024,78 @@ def bicgstab_direction(n, d_num_r, d_den_r, d_num_a, d_den_a, d_num_w, d_den_w, 
     fn = getattr(load(), "spmv_hip_bicgstab_direction_" + _krylov_suffix((d_r, d_v, d_p, d_minv, d_phat), dtype))
     check(fn(n, _addr(d_num_r), _addr(d_den_r), _addr(d_num_a), _addr(d_den_a), _addr(d_num_w), _addr(d_den_w), _addr(d_r), _addr(d_v),
              _addr(d_p), _addr(d_minv), _addr(d_phat), stream))
+
+
+GMRES_MAX_BASIS = 32
+
+
+def gmres_workspace_bytes(n, k_max):
+    """The workspace gmres_project and gmres_update over n elements and up to k_max vectors need (include/spmv_hip_gmres.h): a
+    function of n and k_max alone, at least 16, never decreasing in either."""
+    b = C.c_size_t(0)
+    check(load().spmv_hip_gmres_workspace(n, k_max, C.byref(b)))
+    return b.value
+
+
+def gmres_state_doubles(m):
+    """The doubles of the device state of a cycle of m steps (1 <= m <= GMRES_MAX_BASIS)."""
+    rc = load().spmv_hip_gmres_state_doubles(m)
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def gmres_state_layout(m):
+    """Where the parts of the state lie, as the header documents them: the first index of g (m + 1 doubles), of the cosines, of
+    the sines (m each) and of R (column j starts at r + j (j + 1) / 2)."""
+    return {"g": 2, "c": 3 + m, "s": 3 + 2 * m, "r": 3 + 3 * m}
+
+
+def _work_bytes(d_work, work_bytes):
+    return d_work.numel() * d_work.element_size() if work_bytes is None else work_bytes
+
+
+def gmres_project(n, k, d_V, ldv, d_w, d_h, d_work, work_bytes=None, stream=0, dtype=None):
+    """d_h[j] <- V_j' w for j < k and d_h[k] <- w' w, V_j at d_V + j ldv elements (d_V None where k == 0).  Torch tensors or raw
+    device addresses; float64 or float32 vectors by their dtype (raw addresses: dtype=), d_h always doubles.  work_bytes defaults
+    to the size of a tensor d_work (gmres_workspace_bytes).  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_gmres_project_" + _krylov_suffix((d_V, d_w), dtype))
+    check(fn(n, k, _addr(d_V), ldv, _addr(d_w), _addr(d_h), _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+
+
+def gmres_update(n, k, d_V, ldv, d_h, d_w, d_dots, d_work, work_bytes=None, stream=0, dtype=None):
+    """w <- w - sum_j d_h[j] V_j in place, j ascending, with d_h read on the device, and d_dots <- {w' w of the new w, +0.0}.
+    Arguments as for gmres_project.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_gmres_update_" + _krylov_suffix((d_V, d_w), dtype))
+    check(fn(n, k, _addr(d_V), ldv, _addr(d_h), _addr(d_w), _addr(d_dots), _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+
+
+def gmres_scale(n, d_scale, d_v, d_minv, d_vhat, stream=0, dtype=None):
+    """v <- v d_scale[0] in place with the scale read on the device; with d_minv, d_vhat <- diag(d_minv) v (both None or both
+    given).  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_gmres_scale_" + _krylov_suffix((d_v, d_minv, d_vhat), dtype))
+    check(fn(n, _addr(d_scale), _addr(d_v), _addr(d_minv), _addr(d_vhat), stream))
+
+
+def gmres_correct(n, k, d_V, ldv, d_y, d_minv, d_x, stream=0, dtype=None):
+    """x <- x + diag(d_minv) sum_j d_y[j] V_j (d_minv None: no diagonal), d_y read on the device.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_gmres_correct_" + _krylov_suffix((d_V, d_minv, d_x), dtype))
+    check(fn(n, k, _addr(d_V), ldv, _addr(d_y), _addr(d_minv), _addr(d_x), stream))
+
+
+def gmres_start(m, d_nrm2, d_state, stream=0):
+    """The state of a new cycle of m steps from d_nrm2[0] = r' r: g = beta e_1, state[0] = beta, state[1] = 1 / beta."""
+    check(load().spmv_hip_gmres_start(m, _addr(d_nrm2), _addr(d_state), stream))
+
+
+def gmres_column(k, m, d_h1, d_h2, d_nrm2, d_state, stream=0):
+    """Column k of the cycle: h = h1 + h2 and h_{k+1} = sqrt(d_nrm2[0]) through the stored rotations and a new one."""
+    check(load().spmv_hip_gmres_column(k, m, _addr(d_h1), _addr(d_h2), _addr(d_nrm2), _addr(d_state), stream))
+
+
+def gmres_solve(k, m, d_state, d_y, stream=0):
+    """d_y[0 ... k - 1] <- R[0:k, 0:k]^-1 g[0:k] of the state."""
+    check(load().spmv_hip_gmres_solve(k, m, _addr(d_state), _addr(d_y), stream))
 
 
 class MvPlan:
