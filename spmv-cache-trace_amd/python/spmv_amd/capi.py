@@ -1,6 +1,7 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
-spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h and spmv_hip_gmres.h (the C ABI of libspmv_hip.so).
+spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h and spmv_hip_bjacobi.h (the C ABI of
+libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -26,7 +27,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
-                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h")]
+                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -194,6 +195,13 @@ SIGNATURES = {
     "spmv_hip_gmres_start": (C.c_int, [C.c_int32, _vp, _vp, _vp]),
     "spmv_hip_gmres_column": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "spmv_hip_gmres_solve": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    # spmv_hip_bjacobi.h
+    "spmv_hip_bjacobi_setup_f64": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 6),
+    "spmv_hip_bjacobi_setup_f32": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 6),
+    "spmv_hip_bjacobi_apply_f64": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_bjacobi_apply_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_bjacobi_apply_add_f64": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "spmv_hip_bjacobi_apply_add_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -1207,3 +1215,31 @@ def ell_spmv(rows, row_length, d_col_cm, d_val_cm, d_x, d_y, stream=0):
 def triad(n, d_a, d_b, d_c, q=3.1, stream=0):
     """a = b + q*c on device arrays (STREAM triad, the empirical bandwidth roofline)."""
     check(load().spmv_hip_triad(n, d_a, d_b, d_c, q, stream))
+
+
+BJACOBI_MAX_BLOCK = 8
+
+
+def bjacobi_setup(rows, b, d_row_ptr, d_column_index, d_value, d_inv, d_status, stream=0, dtype=None):
+    """d_inv <- the inverses of the rows / b diagonal blocks of the device CSR arrays (d_value doubles), block k row-major at
+    d_inv + k b b, and d_status (two int32) <- {singular blocks, the first of them or -1} (include/spmv_hip_bjacobi.h).  Torch
+    tensors or raw device addresses; the inverse is float64 or float32 by the dtype of d_inv (a raw address: dtype=).  Only
+    enqueues."""
+    fn = getattr(load(), "spmv_hip_bjacobi_setup_" + _krylov_suffix((d_inv,), dtype))
+    check(fn(rows, b, _addr(d_row_ptr), _addr(d_column_index), _addr(d_value), _addr(d_inv), _addr(d_status), stream))
+
+
+def bjacobi_apply(n, b, d_inv, d_r, d_z, d_dots=None, d_work=None, work_bytes=None, stream=0, dtype=None):
+    """z <- M^-1 r for the block-diagonal inverse d_inv and, with d_dots and d_work (krylov_workspace_bytes(n)), d_dots <-
+    {r' z, z' z} of z as stored.  Arguments as for cg_step; work_bytes defaults to the size of a tensor d_work (0 without one).
+    Only enqueues."""
+    fn = getattr(load(), "spmv_hip_bjacobi_apply_" + _krylov_suffix((d_inv, d_r, d_z), dtype))
+    if work_bytes is None:
+        work_bytes = d_work.numel() * d_work.element_size() if d_work is not None else 0
+    check(fn(n, b, _addr(d_inv), _addr(d_r), _addr(d_z), _addr(d_dots), _addr(d_work), work_bytes, stream))
+
+
+def bjacobi_apply_add(n, b, d_inv, d_u, d_x, stream=0, dtype=None):
+    """x <- x + M^-1 u in place.  Arguments as for bjacobi_apply.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_bjacobi_apply_add_" + _krylov_suffix((d_inv, d_u, d_x), dtype))
+    check(fn(n, b, _addr(d_inv), _addr(d_u), _addr(d_x), stream))
