@@ -1,12 +1,10 @@
 // bicgstab.hip -- include/spmv_hip_bicgstab.h: the three vector updates of a BiCGStab iteration over caller-owned device vectors,
 // their scalars quotients of doubles in device memory.  The kernels are bicgstab_updates.hpp; the workspace rule, the check of a
-// call's arrays (krylov_check.hpp) and the reduction of the step's slots (f32_plan.hpp: dots_reduce) are those of krylov.hip.
+// call's arrays, the launch (krylov_check.hpp) and the reduction of the step's slots (f32_plan.hpp: dots_reduce) are those of krylov.hip.
 #include "spmv_hip_bicgstab.h"
 
 #include "krylov_check.hpp"
 #include "bicgstab_updates.hpp"
-
-#include <cstdio>
 
 using namespace spmvi;
 
@@ -27,15 +25,8 @@ int bicgstab_s(int32_t n, const double * d_num, const double * d_den, const T * 
     const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    const long long slots = krylov_slots(n);
-    if (slots == 0)
-        return SPMV_HIP_OK;
-    void (*kernel)(long long, const double *, const double *, const T *, T *, const T *, T *) =
-        d_minv ? spmv::bicgstab_s_kernel<T, true> : spmv::bicgstab_s_kernel<T, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), (long long) n, d_num, d_den, d_v,
-                       d_r, d_minv, d_shat);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return krylov_launch(d_minv ? spmv::bicgstab_s_kernel<T, true> : spmv::bicgstab_s_kernel<T, false>, krylov_slots(n),
+                         static_cast<hipStream_t>(stream), n, d_num, d_den, d_v, d_r, d_minv, d_shat);
 }
 
 template <class T>
@@ -53,23 +44,19 @@ int bicgstab_step(int32_t n, const double * d_num_a, const double * d_den_a, con
                                   {d_rhat, vec, false, 16, "d_rhat"},     {d_x, vec, true, 16, "d_x"},          {d_r, vec, true, 16, "d_r"},
                                   {d_dots, 16, true, 16, "d_dots"},       {d_work, need, true, 16, "d_work"},   {d_num_a, 8, false, 8, "d_num_a"},
                                   {d_den_a, 8, false, 8, "d_den_a"},      {d_num_w, 8, false, 8, "d_num_w"},    {d_den_w, 8, false, 8, "d_den_w"}};
-    const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    if (work_bytes < need) { // looked at last: a call refused for this alone has arrays that may be launched over
-        char text[160];
-        std::snprintf(text, sizeof text, "work_bytes is %zu and n needs %zu (spmv_hip_krylov_workspace)", work_bytes, need);
-        return fail(SPMV_HIP_ERR_INVALID, text);
-    }
+    // looked at last: a call refused for this alone has arrays that may be launched over
+    rc = krylov_check_work(work_bytes, need, "n", "spmv_hip_krylov_workspace");
+    if (rc != 0)
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long slots = krylov_slots(n);
-    if (slots > 0) {
-        void (*kernel)(long long, const double *, const double *, const double *, const double *, const T *, const T *, const T *, const T *, T *, T *,
-                       spmv::v2d *) = d_shat ? spmv::bicgstab_step_kernel<T, true> : spmv::bicgstab_step_kernel<T, false>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, s, (long long) n, d_num_a, d_den_a, d_num_w, d_den_w, d_phat,
-                           d_shat, d_t, d_rhat, d_x, d_r, static_cast<spmv::v2d *>(d_work));
-        HIP_TRY(hipGetLastError());
-    }
+    rc = krylov_launch(d_shat ? spmv::bicgstab_step_kernel<T, true> : spmv::bicgstab_step_kernel<T, false>, slots, s, n, d_num_a, d_den_a,
+                       d_num_w, d_den_w, d_phat, d_shat, d_t, d_rhat, d_x, d_r, d_work);
+    if (rc != 0)
+        return rc;
     return dots_reduce(DotsArgs{nullptr, d_dots, d_work, work_bytes}, (int) slots, s);
 }
 
@@ -92,15 +79,8 @@ int bicgstab_direction(int32_t n, const double * d_num_r, const double * d_den_r
     const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    const long long slots = krylov_slots(n);
-    if (slots == 0)
-        return SPMV_HIP_OK;
-    void (*kernel)(long long, const double *, const double *, const double *, const double *, const double *, const double *, const T *, const T *,
-                   T *, const T *, T *) = d_minv ? spmv::bicgstab_direction_kernel<T, true> : spmv::bicgstab_direction_kernel<T, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), (long long) n, d_num_r, d_den_r,
-                       d_num_a, d_den_a, d_num_w, d_den_w, d_r, d_v, d_p, d_minv, d_phat);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return krylov_launch(d_minv ? spmv::bicgstab_direction_kernel<T, true> : spmv::bicgstab_direction_kernel<T, false>, krylov_slots(n),
+                         static_cast<hipStream_t>(stream), n, d_num_r, d_den_r, d_num_a, d_den_a, d_num_w, d_den_w, d_r, d_v, d_p, d_minv, d_phat);
 }
 
 } // namespace

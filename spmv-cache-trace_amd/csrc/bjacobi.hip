@@ -1,12 +1,10 @@
 // bjacobi.hip -- include/spmv_hip_bjacobi.h: the point-block Jacobi preconditioner over caller-owned device arrays.  The kernels
-// are bjacobi_kernels.hpp; the cut, the workspace rule and the check of a call's arrays are the conjugate-gradient step's
-// (krylov_check.hpp), the reduction of the apply's slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).
+// are bjacobi_kernels.hpp; the cut, the workspace rule, the check of a call's arrays and the launch are the conjugate-gradient
+// step's (krylov_check.hpp), the reduction of the apply's slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).
 #include "spmv_hip_bjacobi.h"
 
 #include "krylov_check.hpp"
 #include "bjacobi_kernels.hpp"
-
-#include <cstdio>
 
 using namespace spmvi;
 
@@ -27,7 +25,7 @@ int check_block(int32_t n, int32_t b)
 }
 
 template <class T, int MODE>
-void launch_apply(int b, unsigned blocks, hipStream_t s, long long n, const T * inv, const T * r, T * z, spmv::v2d * slots)
+int launch_apply(int b, long long slots, hipStream_t s, int32_t n, const T * inv, const T * r, T * z, void * work)
 {
     void (*kernel)(long long, const T *, const T *, T *, spmv::v2d *) = nullptr;
     switch (b) {
@@ -40,7 +38,7 @@ void launch_apply(int b, unsigned blocks, hipStream_t s, long long n, const T * 
     case 7: kernel = spmv::bjacobi_apply_kernel<T, 7, MODE>; break;
     default: kernel = spmv::bjacobi_apply_kernel<T, 8, MODE>; break;
     }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, n, inv, r, z, slots);
+    return krylov_launch(kernel, slots, s, n, inv, r, z, work);
 }
 
 template <class T>
@@ -89,25 +87,20 @@ int bjacobi_apply(int32_t n, int32_t b, const T * d_inv, const T * d_r, T * d_z,
                                   {d_z, vec, true, 16, "d_z"},
                                   {d_dots, 16, true, 16, "d_dots"},
                                   {d_work, need, true, 16, "d_work"}};
-    const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    if (work_bytes < need) { // looked at last: a call refused for this alone has passed every other check
-        char text[160];
-        std::snprintf(text, sizeof text, "work_bytes is %zu and n needs %zu (spmv_hip_krylov_workspace)", work_bytes, need);
-        return fail(SPMV_HIP_ERR_INVALID, text);
-    }
+    // looked at last: a call refused for this alone has passed every other check
+    rc = krylov_check_work(work_bytes, need, "n", "spmv_hip_krylov_workspace");
+    if (rc != 0)
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long slots = krylov_slots(n);
-    if (slots > 0) {
-        if (d_dots)
-            launch_apply<T, 1>(b, (unsigned) ((slots + 3) / 4), s, (long long) n, d_inv, d_r, d_z, static_cast<spmv::v2d *>(d_work));
-        else
-            launch_apply<T, 0>(b, (unsigned) ((slots + 3) / 4), s, (long long) n, d_inv, d_r, d_z, nullptr);
-        HIP_TRY(hipGetLastError());
-    }
     if (!d_dots)
-        return SPMV_HIP_OK;
+        return launch_apply<T, 0>(b, slots, s, n, d_inv, d_r, d_z, nullptr);
+    rc = launch_apply<T, 1>(b, slots, s, n, d_inv, d_r, d_z, d_work);
+    if (rc != 0)
+        return rc;
     return dots_reduce(DotsArgs{nullptr, d_dots, d_work, work_bytes}, (int) slots, s);
 }
 
@@ -124,12 +117,7 @@ int bjacobi_apply_add(int32_t n, int32_t b, const T * d_inv, const T * d_u, T * 
     const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    const long long slots = krylov_slots(n);
-    if (slots == 0)
-        return SPMV_HIP_OK;
-    launch_apply<T, 2>(b, (unsigned) ((slots + 3) / 4), static_cast<hipStream_t>(stream), (long long) n, d_inv, d_u, d_x, nullptr);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return launch_apply<T, 2>(b, krylov_slots(n), static_cast<hipStream_t>(stream), n, d_inv, d_u, d_x, nullptr);
 }
 
 } // namespace

@@ -1,14 +1,13 @@
 // bjacobi_kernels.hpp -- the point-block Jacobi preconditioner (include/spmv_hip_bjacobi.h).
 //
-// bjacobi_apply_kernel<T, B, MODE> is a streaming kernel over the cut of cg_updates.hpp: chunk c = elements [c kKrylovChunk,
-// (c + 1) kKrylovChunk) belongs to wave c, lane l takes the 16-byte groups l, l + 64, ... of the chunk in that order.  Row i of
-// the block-diagonal inverse is the B elements at inv + i B, so a lane's share of the inverse for one group of the vector is
-// exactly B aligned 16-byte groups, and the wave's share for 64 groups is 64 B consecutive ones: the dominant stream is 16-byte
-// loads of which every byte of every line is used.  A block's r entries straddle lanes, groups and chunks (1024 is no multiple
-// of 3, 5, 6 or 7): unless the block lies in the lane's own group (B == 1, 2, and 4 in floats) they are loaded by address -- as
-// 16-byte groups where a block is whole groups, as scalars otherwise -- and come from the vector cache, which neighbouring lanes
-// and the lane's own group load have just filled: r leaves HBM once.  B is a template parameter: i / B is a multiplication and
-// every register array is indexed statically.  No LDS, no barrier, no atomics; offsets into the inverse are 64-bit.
+// bjacobi_apply_kernel<T, B, MODE> is a streaming kernel over the cut of krylov_stream.hpp.  Row i of the block-diagonal inverse
+// is the B elements at inv + i B, so a lane's share of the inverse for one group of the vector is exactly B aligned 16-byte
+// groups, and the wave's share for 64 groups is 64 B consecutive ones: the dominant stream is 16-byte loads of which every byte
+// of every line is used.  A block's r entries straddle lanes, groups and chunks (1024 is no multiple of 3, 5, 6 or 7): unless
+// the block lies in the lane's own group (B == 1, 2, and 4 in floats) they are loaded by address -- as 16-byte groups where a
+// block is whole groups, as scalars otherwise -- and come from the vector cache, which neighbouring lanes and the lane's own
+// group load have just filled: r leaves HBM once.  B is a template parameter: i / B is a multiplication and every register array
+// is indexed statically.  No LDS, no barrier, no atomics; offsets into the inverse are 64-bit.
 // MODE 0: z <- M^-1 r; MODE 1: ... with slots[chunk] = {sum z r, sum z z} of z as stored (store_wave_dots); MODE 2: z <- z + M^-1 r.
 //
 // bjacobi_setup_kernel<T> is one-time code: one wave (a workgroup of 64) per block.  The wave scans each of the block's rows 64
@@ -143,11 +142,11 @@ __global__ __launch_bounds__(256, (bjacobi_waves<T, B>())) void bjacobi_apply_ke
     constexpr int W = 16 / (int) sizeof(T);
     constexpr int GROUPS = kKrylovChunk / W;
     constexpr int PER_LANE = GROUPS / kWave;
-    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
-    const long long chunk = (long long) blockIdx.x * 4 + wave;
-    if (chunk * kKrylovChunk >= n)
-        return; // the whole wave: no slot behind the last element
-    const int lane = (int) threadIdx.x & (kWave - 1);
+    const KrylovWave at = krylov_wave(n);
+    if (!at.any)
+        return;
+    const long long chunk = at.chunk;
+    const int lane = at.lane();
     const G * ig = reinterpret_cast<const G *>(inv);
     G * zg = reinterpret_cast<G *>(z);
     const long long g0 = chunk * GROUPS + lane;

@@ -7,8 +7,6 @@
 #include "krylov_check.hpp"
 #include "gmres_updates.hpp"
 
-#include <cstdio>
-
 using namespace spmvi;
 
 static_assert(spmv::kGmresMaxBasis == SPMV_HIP_GMRES_MAX_BASIS, "the header documents the largest basis");
@@ -41,16 +39,7 @@ int basis_check(int32_t n, int32_t k, const T * d_V, long long ldv, unsigned lon
     return SPMV_HIP_OK;
 }
 
-int work_check(size_t work_bytes, size_t need)
-{
-    if (work_bytes >= need)
-        return SPMV_HIP_OK;
-    char text[160];
-    std::snprintf(text, sizeof text, "work_bytes is %zu and the call needs %zu (spmv_hip_gmres_workspace)", work_bytes, need);
-    return fail(SPMV_HIP_ERR_INVALID, text);
-}
-
-unsigned blocks_of(long long slots) { return (unsigned) ((slots + 3) / 4); }
+int work_check(size_t work_bytes, size_t need) { return krylov_check_work(work_bytes, need, "the call", "spmv_hip_gmres_workspace"); }
 
 template <class T>
 int gmres_project(int32_t n, int32_t k, const T * d_V, long long ldv, const T * d_w, double * d_h, void * d_work, size_t work_bytes, void * stream)
@@ -76,11 +65,9 @@ int gmres_project(int32_t n, int32_t k, const T * d_V, long long ldv, const T * 
     const long long slots = krylov_slots(n), stride = pair_stride(n);
     const unsigned pairs = (unsigned) project_pairs(k);
     spmv::v2d * work = static_cast<spmv::v2d *>(d_work);
-    if (slots > 0) {
-        hipLaunchKernelGGL(spmv::gmres_project_kernel<T>, dim3(blocks_of(slots)), dim3(256), 0, s, (long long) n, (int) k, d_V, ldv, d_w,
-                           static_cast<double *>(d_work), stride);
-        HIP_TRY(hipGetLastError());
-    }
+    rc = krylov_launch(spmv::gmres_project_kernel<T>, slots, s, n, k, d_V, ldv, d_w, d_work, stride);
+    if (rc != 0)
+        return rc;
     // dots_reduce's stages, for every pair at once
     const long long blocks = reduce_blocks(slots);
     if (blocks > 1) {
@@ -120,11 +107,9 @@ int gmres_update(int32_t n, int32_t k, const T * d_V, long long ldv, const doubl
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long slots = krylov_slots(n);
-    if (slots > 0) {
-        hipLaunchKernelGGL((spmv::gmres_axpys_kernel<T, spmv::kGmresUpdate>), dim3(blocks_of(slots)), dim3(256), 0, s, (long long) n, (int) k, d_V, ldv,
-                           d_h, d_w, (const T *) nullptr, static_cast<spmv::v2d *>(d_work));
-        HIP_TRY(hipGetLastError());
-    }
+    rc = krylov_launch(spmv::gmres_axpys_kernel<T, spmv::kGmresUpdate>, slots, s, n, k, d_V, ldv, d_h, d_w, nullptr, d_work);
+    if (rc != 0)
+        return rc;
     return dots_reduce(DotsArgs{nullptr, d_dots, d_work, work_bytes}, (int) slots, s);
 }
 
@@ -145,13 +130,8 @@ int gmres_scale(int32_t n, const double * d_scale, T * d_v, const T * d_minv, T 
     const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    const long long slots = krylov_slots(n);
-    if (slots == 0)
-        return SPMV_HIP_OK;
-    void (*kernel)(long long, const double *, T *, const T *, T *) = d_minv ? spmv::gmres_scale_kernel<T, true> : spmv::gmres_scale_kernel<T, false>;
-    hipLaunchKernelGGL(kernel, dim3(blocks_of(slots)), dim3(256), 0, static_cast<hipStream_t>(stream), (long long) n, d_scale, d_v, d_minv, d_vhat);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return krylov_launch(d_minv ? spmv::gmres_scale_kernel<T, true> : spmv::gmres_scale_kernel<T, false>, krylov_slots(n),
+                         static_cast<hipStream_t>(stream), n, d_scale, d_v, d_minv, d_vhat);
 }
 
 template <class T>
@@ -171,15 +151,10 @@ int gmres_correct(int32_t n, int32_t k, const T * d_V, long long ldv, const doub
     rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    const long long slots = krylov_slots(n);
-    if (slots == 0 || k == 0)
+    if (k == 0)
         return SPMV_HIP_OK;
-    void (*kernel)(long long, int, const T *, long long, const double *, T *, const T *, spmv::v2d *) =
-        d_minv ? spmv::gmres_axpys_kernel<T, spmv::kGmresCorrectM> : spmv::gmres_axpys_kernel<T, spmv::kGmresCorrect>;
-    hipLaunchKernelGGL(kernel, dim3(blocks_of(slots)), dim3(256), 0, static_cast<hipStream_t>(stream), (long long) n, (int) k, d_V, ldv, d_y, d_x,
-                       d_minv, (spmv::v2d *) nullptr);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return krylov_launch(d_minv ? spmv::gmres_axpys_kernel<T, spmv::kGmresCorrectM> : spmv::gmres_axpys_kernel<T, spmv::kGmresCorrect>,
+                         krylov_slots(n), static_cast<hipStream_t>(stream), n, k, d_V, ldv, d_y, d_x, d_minv, nullptr);
 }
 
 bool basis_size(int32_t m) { return m >= 1 && m <= SPMV_HIP_GMRES_MAX_BASIS; }

@@ -1,7 +1,5 @@
 // gmres_updates.hpp -- the kernels of restarted GMRES with classical Gram-Schmidt applied twice (include/spmv_hip_gmres.h), over
-// the cut of cg_updates.hpp: chunk c = elements [c kKrylovChunk, (c + 1) kKrylovChunk) belongs to wave c of the grid (four to a
-// workgroup), lane l of that wave takes the 16-byte groups l, l + 64, ... of the chunk in that order, and the up to 3 elements
-// behind the vector's last whole group go last, to lanes 0, 1, 2 of the last chunk.
+// the cut of krylov_stream.hpp.
 //
 //   project   h[j] = V_j' w, h[k] = w' w.  The basis is blocked in registers, at most kGmresBlock vectors at a time: the chunk is the outer
 //             loop and the block the inner one, so every V_j is streamed once and the chunk's w (8 KiB, 4 KiB of floats) is read
@@ -13,7 +11,7 @@
 //             correction (x += u or x += m u, u = sum y_j V_j).  A lane keeps the running values of its WHOLE share of the chunk
 //             (16 elements) and reads a vector's 8 KiB of the chunk in one go, two vectors in flight: passes of a quarter of the
 //             chunk over all vectors, returning to every vector four times, ran a quarter slower at k = 16.
-//   scale     v *= scale[0] in place and, with minv, vhat = m v.
+//   scale     v *= scale[0] in place and, with minv, vhat = m v: element-wise, on krylov_stream.
 //   reduce    dots_reduce_block (csr_dots.hpp) over the slots of each pair of vectors: the order of dots_reduce for that many slots.
 //   start, column, solve   the Hessenberg bookkeeping of one cycle, one workgroup each.
 //
@@ -121,11 +119,11 @@ template <class T>
 __global__ __launch_bounds__(256) void gmres_project_kernel(long long n, int k, const T * V, long long ldv, const T * w, double * __restrict__ slots,
                                                             long long stride)
 {
-    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
-    const long long chunk = (long long) blockIdx.x * 4 + wave;
-    if (chunk * kKrylovChunk >= n)
-        return; // the whole wave: no slot behind the last element
-    const int lane = (int) threadIdx.x & (kWave - 1);
+    const KrylovWave at = krylov_wave(n);
+    if (!at.any)
+        return;
+    const long long chunk = at.chunk;
+    const int lane = at.lane();
     // k + 1 vectors (w itself the last) in the fewest blocks of at most kGmresBlock, of equal size but for one vector: no
     // block of one or two vectors behind whole ones, whose few loads would leave the wave waiting on every pass
     const int total = k + 1, nblocks = (total + kGmresBlock - 1) / kGmresBlock;
@@ -201,11 +199,11 @@ __global__ __launch_bounds__(256, 4) void gmres_axpys_kernel(long long n, int k,
     constexpr int GROUPS = kKrylovChunk / W;
     constexpr int PER_LANE = GROUPS / kWave, U = PER_LANE, JU = 2; // the lane's whole share of the chunk, of JU vectors at a time
     static_assert(PER_LANE % U == 0, "whole passes");
-    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
-    const long long chunk = (long long) blockIdx.x * 4 + wave;
-    if (chunk * kKrylovChunk >= n)
+    const KrylovWave at = krylov_wave(n);
+    if (!at.any)
         return;
-    const int lane = (int) threadIdx.x & (kWave - 1);
+    const long long chunk = at.chunk;
+    const int lane = at.lane();
     G * yg = reinterpret_cast<G *>(y);
     const G * mg = reinterpret_cast<const G *>(minv);
     const long long g0 = chunk * GROUPS + lane;
@@ -338,76 +336,13 @@ template <class T, bool HASM>
 __global__ __launch_bounds__(256, 8) void gmres_scale_kernel(long long n, const double * __restrict__ scale, T * __restrict__ v,
                                                              const T * __restrict__ minv, T * __restrict__ vhat)
 {
-    typedef typename KrylovGroup<T>::type G;
-    constexpr int W = 16 / (int) sizeof(T);
-    constexpr int GROUPS = kKrylovChunk / W;
-    constexpr int PER_LANE = GROUPS / kWave, U = HASM ? 2 : 4;
-    static_assert(PER_LANE % U == 0, "whole passes");
-    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
-    const long long chunk = (long long) blockIdx.x * 4 + wave;
-    if (chunk * kKrylovChunk >= n)
+    const KrylovWave at = krylov_wave(n);
+    if (!at.any)
         return;
-    const int lane = (int) threadIdx.x & (kWave - 1);
     const double s = scale[0];
-    G * vg = reinterpret_cast<G *>(v);
-    const G * mg = reinterpret_cast<const G *>(minv);
-    G * hg = reinterpret_cast<G *>(vhat);
-    const long long g0 = chunk * GROUPS + lane;
-    if ((chunk + 1) * kKrylovChunk <= n) {
-#pragma unroll 1
-        for (int j = 0; j < PER_LANE; j += U) {
-            G vv[U], vm[U], vh[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long long g = g0 + (long long) (j + u) * kWave;
-                vv[u] = vg[g];
-                if (HASM)
-                    vm[u] = mg[g];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long long g = g0 + (long long) (j + u) * kWave;
-#pragma unroll
-                for (int c = 0; c < W; ++c) {
-                    T a = vv[u][c], b = (T) 0;
-                    gmres_scale_element<T, HASM>(s, HASM ? vm[u][c] : (T) 0, a, b);
-                    vv[u][c] = a;
-                    vh[u][c] = b;
-                }
-                vg[g] = vv[u];
-                if (HASM)
-                    hg[g] = vh[u];
-            }
-        }
-    } else {
-        const long long ngroups = n / W;
-        for (int j = 0; j < PER_LANE; ++j) {
-            const long long g = g0 + (long long) j * kWave;
-            if (g < ngroups) {
-                G vv = vg[g], vm = vv, vh = vv;
-                if (HASM)
-                    vm = mg[g];
-#pragma unroll
-                for (int c = 0; c < W; ++c) {
-                    T a = vv[c], b = (T) 0;
-                    gmres_scale_element<T, HASM>(s, vm[c], a, b);
-                    vv[c] = a;
-                    vh[c] = b;
-                }
-                vg[g] = vv;
-                if (HASM)
-                    hg[g] = vh;
-            }
-        }
-        const long long t = ngroups * W + lane;
-        if (t < n) {
-            T a = v[t], b = (T) 0;
-            gmres_scale_element<T, HASM>(s, HASM ? minv[t] : (T) 0, a, b);
-            v[t] = a;
-            if (HASM)
-                vhat[t] = b;
-        }
-    }
+    const T * const arrays[] = {v, minv, vhat};
+    krylov_stream<T, HASM ? 2 : 4, false, kKrylovUpdate, HASM ? kKrylovRead : kKrylovAbsent, HASM ? kKrylovWrite : kKrylovAbsent>(
+        n, at, arrays, [&](T * e) { gmres_scale_element<T, HASM>(s, e[1], e[0], e[2]); });
 }
 
 // ---- the state of one cycle (include/spmv_hip_gmres.h documents the layout) --------------------------------------------------------

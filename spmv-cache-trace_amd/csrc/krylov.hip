@@ -1,7 +1,7 @@
 // krylov.hip -- include/spmv_hip_krylov.h: the step and the direction of a conjugate-gradient iteration over caller-owned device
 // vectors, their scalar a quotient of two doubles in device memory.  The kernels are cg_updates.hpp; the reduction of the step's
-// slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).  The workspace rule and the check of a call's arrays
-// are shared with bicgstab.hip (krylov_check.hpp).
+// slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).  The workspace rule, the check of a call's arrays and
+// the launch over the chunk grid are shared with bicgstab.hip, gmres.hip and bjacobi.hip (krylov_check.hpp).
 #include "spmv_hip_krylov.h"
 
 #include "krylov_check.hpp"
@@ -39,6 +39,15 @@ int krylov_check_arrays(int32_t n, size_t elem, const KrylovArray * arrays, int 
     return SPMV_HIP_OK;
 }
 
+int krylov_check_work(size_t work_bytes, size_t need, const char * what, const char * rule)
+{
+    if (work_bytes >= need)
+        return SPMV_HIP_OK;
+    char text[160];
+    std::snprintf(text, sizeof text, "work_bytes is %zu and %s needs %zu (%s)", work_bytes, what, need, rule);
+    return fail(SPMV_HIP_ERR_INVALID, text);
+}
+
 } // namespace spmvi
 
 namespace {
@@ -52,27 +61,22 @@ int cg_step(int32_t n, const double * d_num, const double * d_den, const T * d_p
     if (!d_num || !d_den || !d_p || !d_q || !d_x || !d_r || !d_dots || !d_work)
         return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_minv may be null)");
     const size_t need = krylov_bytes(n);
-    if (work_bytes < need) {
-        char text[160];
-        std::snprintf(text, sizeof text, "work_bytes is %zu and n needs %zu (spmv_hip_krylov_workspace)", work_bytes, need);
-        return fail(SPMV_HIP_ERR_INVALID, text);
-    }
+    int rc = krylov_check_work(work_bytes, need, "n", "spmv_hip_krylov_workspace");
+    if (rc != 0)
+        return rc;
     const unsigned long long vec = (unsigned long long) n * sizeof(T);
     const KrylovArray arrays[] = {{d_p, vec, false, 16, "d_p"},       {d_q, vec, false, 16, "d_q"},       {d_x, vec, true, 16, "d_x"},
                                   {d_r, vec, true, 16, "d_r"},        {d_minv, vec, false, 16, "d_minv"}, {d_dots, 16, true, 16, "d_dots"},
                                   {d_work, need, true, 16, "d_work"}, {d_num, 8, false, 8, "d_num"},      {d_den, 8, false, 8, "d_den"}};
-    const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long slots = krylov_slots(n);
-    if (slots > 0) {
-        void (*kernel)(long long, const double *, const double *, const T *, const T *, T *, T *, const T *, spmv::v2d *) =
-            d_minv ? spmv::cg_step_kernel<T, true> : spmv::cg_step_kernel<T, false>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, s, (long long) n, d_num, d_den, d_p, d_q, d_x, d_r, d_minv,
-                           static_cast<spmv::v2d *>(d_work));
-        HIP_TRY(hipGetLastError());
-    }
+    rc = krylov_launch(d_minv ? spmv::cg_step_kernel<T, true> : spmv::cg_step_kernel<T, false>, slots, s, n, d_num, d_den, d_p, d_q, d_x, d_r,
+                       d_minv, d_work);
+    if (rc != 0)
+        return rc;
     return dots_reduce(DotsArgs{nullptr, d_dots, d_work, work_bytes}, (int) slots, s);
 }
 
@@ -89,15 +93,8 @@ int cg_direction(int32_t n, const double * d_num, const double * d_den, const T 
     const int rc = krylov_check_arrays(n, sizeof(T), arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    const long long slots = krylov_slots(n);
-    if (slots == 0)
-        return SPMV_HIP_OK;
-    void (*kernel)(long long, const double *, const double *, const T *, const T *, T *) =
-        d_minv ? spmv::cg_direction_kernel<T, true> : spmv::cg_direction_kernel<T, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned) ((slots + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), (long long) n, d_num, d_den, d_r,
-                       d_minv, d_p);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return krylov_launch(d_minv ? spmv::cg_direction_kernel<T, true> : spmv::cg_direction_kernel<T, false>, krylov_slots(n),
+                         static_cast<hipStream_t>(stream), n, d_num, d_den, d_r, d_minv, d_p);
 }
 
 } // namespace

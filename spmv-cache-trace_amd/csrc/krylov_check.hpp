@@ -1,5 +1,6 @@
-// krylov_check.hpp -- what bicgstab.hip takes from krylov.hip: the workspace rule of a step's dots and the table-driven check of
-// the arrays of one call (include/spmv_hip_krylov.h, include/spmv_hip_bicgstab.h).
+// krylov_check.hpp -- what bicgstab.hip, gmres.hip and bjacobi.hip take from krylov.hip: the workspace rule of a step's dots, the
+// table-driven check of the arrays of one call and the launch over the chunk grid of krylov_stream.hpp
+// (include/spmv_hip_krylov.h, include/spmv_hip_bicgstab.h, include/spmv_hip_gmres.h, include/spmv_hip_bjacobi.h).
 #pragma once
 
 #include "f32_plan.hpp"
@@ -22,5 +23,22 @@ struct KrylovArray {
 
 // what the updates refuse, in the order of spmv_hip_dots.h: null, (the workspace's size: the caller), alignment, 4 GiB, overlaps
 int krylov_check_arrays(int32_t n, size_t elem, const KrylovArray * arrays, int count);
+
+// the workspace's size, where the caller looks at it: "work_bytes is ... and <what> needs ... (<rule>)", rule the function that tells
+int krylov_check_work(size_t work_bytes, size_t need, const char * what, const char * rule);
+
+// workgroups of four waves, a wave per chunk and slot
+inline unsigned krylov_blocks(long long slots) { return (unsigned) ((slots + 3) / 4); }
+
+// one launch of `kernel` over the chunk grid on s, every argument converted to its parameter's type; no slot, no launch
+template <class... P, class... A>
+int krylov_launch(void (*kernel)(P...), long long slots, hipStream_t s, A... args)
+{
+    if (slots == 0)
+        return SPMV_HIP_OK;
+    hipLaunchKernelGGL(kernel, dim3(krylov_blocks(slots)), dim3(256), 0, s, static_cast<P>(args)...);
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
 
 } // namespace spmvi

@@ -34,7 +34,7 @@ SHIPPED = {
     "gmres_axpys_kernelIdLi0E": (98, 4, True), "gmres_axpys_kernelIdLi1E": (82, 5, True), "gmres_axpys_kernelIdLi2E": (84, 5, True),
     "gmres_axpys_kernelIfLi0E": (104, 4, True), "gmres_axpys_kernelIfLi1E": (78, 6, True), "gmres_axpys_kernelIfLi2E": (98, 4, True),
     "gmres_scale_kernelIdLb1E": (24, 8, True), "gmres_scale_kernelIdLb0E": (24, 8, True),
-    "gmres_scale_kernelIfLb1E": (40, 8, True), "gmres_scale_kernelIfLb0E": (54, 8, True),
+    "gmres_scale_kernelIfLb1E": (36, 8, True), "gmres_scale_kernelIfLb0E": (54, 8, True),
     "gmres_reduce_kernelILi256E": (16, 8, False), "gmres_start_kernelE": (12, 8, False), "gmres_column_kernelE": (39, 8, False),
     "gmres_solve_kernelE": (12, 8, False),
 }
