@@ -1,7 +1,7 @@
 // krylov.hip -- include/spmv_hip_krylov.h: the step and the direction of a conjugate-gradient iteration over caller-owned device
 // vectors, their scalar a quotient of two doubles in device memory.  The kernels are cg_updates.hpp; the reduction of the step's
 // slots is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).  The workspace rule, the check of a call's arrays and
-// the launch over the chunk grid are shared with bicgstab.hip, gmres.hip and bjacobi.hip (krylov_check.hpp).
+// the launch over the chunk grid are shared with bicgstab.hip, gmres.hip, bjacobi.hip and cheby.hip (krylov_check.hpp).
 #include "spmv_hip_krylov.h"
 
 #include "krylov_check.hpp"

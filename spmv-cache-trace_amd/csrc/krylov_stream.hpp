@@ -1,5 +1,5 @@
 // krylov_stream.hpp -- the cut of a vector that every Krylov update kernel streams over (cg_updates.hpp, bicgstab_updates.hpp,
-// gmres_updates.hpp, bjacobi_kernels.hpp), written once.  The kernels are shaped as triad_kernel is -- 16-byte loads and stores,
+// gmres_updates.hpp, bjacobi_kernels.hpp, cheby_updates.hpp), written once.  The kernels are shaped as triad_kernel is -- 16-byte loads and stores,
 // several independent loads per lane in flight -- over a FIXED cut: chunk c = elements [c kKrylovChunk, (c + 1) kKrylovChunk)
 // belongs to wave c of the grid (four to a workgroup), and lane l of that wave takes the 16-byte groups l, l + 64, ... of the
 // chunk in that order.  Whole chunks run in unrolled passes of U groups per array without a bounds test; the last chunk of a
@@ -9,7 +9,7 @@
 // csr_dots.hpp: every lane of the wave is active again by then); dots_reduce_kernel adds the slots behind it.  No LDS, no
 // barrier, no atomics; every offset is 64-bit.
 //
-// krylov_wave is the prologue of all nine kernels.  krylov_stream is the whole body of the element-wise ones: it owns the arrays,
+// krylov_wave is the prologue of all ten kernels.  krylov_stream is the whole body of the element-wise ones: it owns the arrays,
 // the vector registers and the three paths, and calls the kernel's function on the SCALARS of one element (functors
 // over structs of whole vectors spill).
 #pragma once

@@ -1,7 +1,7 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
-spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h and spmv_hip_bjacobi.h (the C ABI of
-libspmv_hip.so).
+spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h and
+spmv_hip_cheby.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -27,7 +27,8 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                 for n in ("spmv_hip_tuning.h", "spmv_hip_plan.h", "spmv_hip_symmetric.h", "spmv_hip_multivec.h",
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
-                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h")]
+                                          "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h",
+                                          "spmv_hip_cheby.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -202,6 +203,12 @@ SIGNATURES = {
     "spmv_hip_bjacobi_apply_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "spmv_hip_bjacobi_apply_add_f64": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "spmv_hip_bjacobi_apply_add_f32": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    # spmv_hip_cheby.h
+    "spmv_hip_cheby_bound_f64": (C.c_int, [C.c_int32] + [_vp] * 5),
+    "spmv_hip_cheby_bound_f32": (C.c_int, [C.c_int32] + [_vp] * 5),
+    "spmv_hip_cheby_coeffs": (C.c_int, [C.c_int32, _vp, C.c_double, C.c_double, _vp, _vp]),
+    "spmv_hip_cheby_step_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8 + [C.c_size_t, _vp]),
+    "spmv_hip_cheby_step_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8 + [C.c_size_t, _vp]),
 }
 
 
@@ -1243,3 +1250,33 @@ def bjacobi_apply_add(n, b, d_inv, d_u, d_x, stream=0, dtype=None):
     """x <- x + M^-1 u in place.  Arguments as for bjacobi_apply.  Only enqueues."""
     fn = getattr(load(), "spmv_hip_bjacobi_apply_add_" + _krylov_suffix((d_inv, d_u, d_x), dtype))
     check(fn(n, b, _addr(d_inv), _addr(d_u), _addr(d_x), stream))
+
+
+CHEBY_MAX_DEGREE = 16
+
+
+def cheby_bound(rows, d_row_ptr, d_value, d_minv, d_lambda, stream=0, dtype=None):
+    """d_lambda (one double) <- max_i |d_minv[i]| sum_j |a_ij| of the device CSR arrays (d_value doubles; d_minv None: 1): the
+    Gershgorin bound on lambda_max(M^-1 A) (include/spmv_hip_cheby.h).  Torch tensors or raw device addresses; d_minv is float64
+    or float32 by its dtype (a raw address: dtype=; None without dtype=: float64).  Only enqueues."""
+    suffix = "f64" if d_minv is None and dtype is None else _krylov_suffix((d_minv,), dtype)
+    fn = getattr(load(), "spmv_hip_cheby_bound_" + suffix)
+    check(fn(rows, _addr(d_row_ptr), _addr(d_value), _addr(d_minv), _addr(d_lambda), stream))
+
+
+def cheby_coeffs(degree, d_lambda, scale, ratio, d_coef, stream=0):
+    """d_coef (2 degree doubles) <- the pairs {coef[2j], coef[2j + 1]} of the Chebyshev recurrence over [scale lambda / ratio,
+    scale lambda], lambda = d_lambda[0] read on the device; scale and ratio are host doubles.  Only enqueues."""
+    check(load().spmv_hip_cheby_coeffs(degree, _addr(d_lambda), scale, ratio, _addr(d_coef), stream))
+
+
+def cheby_step(n, degree, j, d_coef, d_u, d_minv, d_d, d_z, d_r=None, d_dots=None, d_work=None, work_bytes=None, stream=0, dtype=None):
+    """Step j of `degree`: d <- coef[2j] d + coef[2j + 1] diag(d_minv) u (d_minv None: u as it is), z <- z + d (j == 0: d and z are
+    not read; j == degree - 1: d is not stored; degree == 1: d_d may be None) with the pair read on the device, and -- the last step
+    alone, with d_r, d_dots and d_work (krylov_workspace_bytes(n)) -- d_dots <- {r' z, z' z} of z as stored.  Arguments as for
+    cg_step; work_bytes defaults to the size of a tensor d_work (0 without one).  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_cheby_step_" + _krylov_suffix((d_u, d_minv, d_d, d_z, d_r), dtype))
+    if work_bytes is None:
+        work_bytes = d_work.numel() * d_work.element_size() if d_work is not None else 0
+    check(fn(n, degree, j, _addr(d_coef), _addr(d_u), _addr(d_minv), _addr(d_d), _addr(d_z), _addr(d_r), _addr(d_dots), _addr(d_work),
+             work_bytes, stream))
