@@ -47,6 +47,20 @@ int check_row_ptr_order(int32_t rows, const int32_t * rp)
     return SPMV_HIP_OK;
 }
 
+int upload_csr_prelude(const spmv_hip_ctx * c, const char * multi, const char * exact, int32_t rows, int32_t cols, int32_t nnz,
+                       const int32_t * row_ptr, const int32_t * column_index, const double * value)
+{
+    if (!c)
+        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
+    if (c->multi)
+        return fail(SPMV_HIP_ERR_STATE, multi);
+    if (exact && (c->flags & SPMV_HIP_FLAG_EXACT_ORDER))
+        return fail(SPMV_HIP_ERR_INVALID, exact);
+    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
+    return SPMV_HIP_OK;
+}
+
 std::string last_error_text() { return g_last_error; }
 void set_last_error_text(std::string const & text) { g_last_error = text; }
 

@@ -2,8 +2,10 @@
 // (include/spmv_hip_compact_f64.h) and y <- fl32(y + fl32(A) x) on float x and y (include/spmv_hip_compact_f32xy.h), with the columns of a tile as 16-bit codes (a 3-bit window number and a 13-bit offset from one of
 // eight per-tile bases).  The tiles are f32values.hip's own (f32_plan.hpp): its descriptors as they
 // are, with the compact bits and the tile's first code quad added; the bases and the codes are made on the host by a few
-// threads, tile by tile; the kernel is csr_compact.hpp.
-#include "f32_plan.hpp"
+// threads, tile by tile; the kernel is csr_compact.hpp.  The multiplies' refusals and launches are tile_front.hpp's: this file
+// describes its three families to it (C16Family).  Level 1 of formats 7 to 10 is here too, once for both plans: the upload
+// (upload_float_tile) and the multiply of a context on its own arrays (ctx_tile_multiply).
+#include "tile_front.hpp"
 #include "csr_compact.hpp"
 
 #include <algorithm>
@@ -87,11 +89,8 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
     pl.flags = flags;
     if (nnz > 0 && !col)
         return fail(SPMV_HIP_ERR_INVALID, "host_column_index is null");
-    bool bad = false;
-    for (int32_t e = 0; e < nnz; ++e)
-        bad |= col[e] < 0 || col[e] >= cols;
-    if (bad)
-        return fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)");
+    if ((rc = check_columns(nnz, col, cols)) != 0)
+        return rc;
     const int nt = fp.numbers.ntiles;
     if (nt == 0)
         return SPMV_HIP_OK; // the multiply does nothing
@@ -220,140 +219,128 @@ int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
 }
 
 // spmv_hip_csr_spmv_c16 (V = float, T = double), spmv_hip_csr_spmv_c16_f64 (V = double) and spmv_hip_csr_spmv_c16_f32xy (V = T =
-// float): the plan knows neither the value type nor the vectors' element type.  With a scale (spmv_hip_scaled.h) d_y is y_out
-// and the same refusals apply; without one it is y += A x.
+// float), three families over one plan, which knows neither the value type nor the vectors' element type.  csr_compact.hpp's
+// kernels take the descriptors, the bases and the codes in front of the arrays; the 32-bit columns are read by wide tiles alone.
+template <class V, class T>
+struct C16Family {
+    const spmv_hip_c16_plan * pl;
+    static const char * null_columns() { return "d_column_index is null and the plan has wide tiles, which read the 32-bit columns"; }
+    bool columns_read() const { return pl->wide_tiles > 0; }
+    // this family's among the three kernels of a launch shape
+    template <class A, class B, class D>
+    static auto mine(A f32xy, B c16, D c16_f64)
+    {
+        if constexpr (std::is_same<T, float>::value)
+            return f32xy;
+        else if constexpr (std::is_same<V, float>::value)
+            return c16;
+        else
+            return c16_f64;
+    }
+    static auto plain(bool x32)
+    {
+        return with_bools([](auto X) { return mine(spmv::csr_compact_f32xy_kernel<X()>, spmv::csr_compact_kernel<X()>, spmv::csr_compact_f64_kernel<X()>); }, x32);
+    }
+    static auto scaled(bool x32, bool beta0)
+    {
+        return with_bools([](auto X, auto B0) { return mine(spmv::csr_compact_f32xy_scaled_kernel<X(), B0()>, spmv::csr_compact_scaled_kernel<X(), B0()>,
+                                                            spmv::csr_compact_f64_scaled_kernel<X(), B0()>); }, x32, beta0);
+    }
+    static auto dots(bool beta0, bool hasw)
+    {
+        return with_bools([](auto B0, auto W) { return mine(spmv::csr_compact_f32xy_scaled_dots_kernel<B0(), W()>, spmv::csr_compact_scaled_dots_kernel<B0(), W()>,
+                                                            spmv::csr_compact_f64_scaled_dots_kernel<B0(), W()>); }, beta0, hasw);
+    }
+    template <class K, class... A>
+    void launch(K kernel, dim3 grid, hipStream_t s, A... a) const
+    {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, a...);
+    }
+};
+
 template <class V, class T>
 int c16_multiply(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const V * d_value,
                  const T * d_x, T * d_y, void * stream, const ScaledArgs<T> * scale = nullptr, const DotsArgs * dots = nullptr)
 {
-    if (!pl)
-        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
-    if (d_x && (const void *) d_x == (const void *) d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (scale) {
-        int rc = scaled_vectors_check(pl->rows, sizeof(T), scale->beta, scale->y_in, d_y);
-        if (rc == 0 && dots)
-            rc = dots_check(*dots, pl->ntiles, pl->rows, pl->cols, pl->nnz, sizeof(T), sizeof(V), d_row_ptr, d_column_index, d_value, d_x,
-                            scale->beta, scale->y_in, d_y);
-        if (rc != 0)
-            return rc;
-        if (pl->rows == 0)
-            return dots ? dots_reduce(*dots, 0, s) : SPMV_HIP_OK;
-        if (scale->alpha == 0.0 || pl->ntiles == 0) { // the beta part alone: neither the matrix nor x is read
-            if (dots)
-                return scaled_rows_only_dots(pl->rows, std::is_same<T, float>::value, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in,
-                                             d_y, *dots, s);
-            return scaled_rows_only(pl->rows, std::is_same<T, float>::value, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, s);
-        }
-    }
-    if (pl->ntiles == 0) // rows, cols or nnz of zero
-        return SPMV_HIP_OK;
-    if (!d_row_ptr || !d_value || !d_x || !d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
-    if (!d_column_index && pl->wide_tiles > 0)
-        return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null and the plan has wide tiles, which read the 32-bit columns");
-    if (!aligned16(d_column_index) || !aligned16(d_value))
-        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
-    if constexpr (std::is_same<T, float>::value) // (the kernel reads and writes x and y one element at a time)
-        if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_y)) & 3u)
-            return fail(SPMV_HIP_ERR_ALIGN, "d_x and d_y must be 4-byte aligned");
-    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
-    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
-    const bool x32 = (long long) pl->cols * (long long) sizeof(T) < (1LL << 32);
-    if (dots) { // (x32 holds: dots_check)
-        const bool beta0 = scale->beta == 0.0, hasw = dots->w != nullptr;
-        void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, double, double,
-                       const T *, T *, const T *, spmv::v2d *, int);
-#define SPMV_C16_PICK(NAME) (beta0 ? (hasw ? spmv::NAME<true, true> : spmv::NAME<true, false>) : (hasw ? spmv::NAME<false, true> : spmv::NAME<false, false>))
-        if constexpr (std::is_same<T, float>::value)
-            kernel = SPMV_C16_PICK(csr_compact_f32xy_scaled_dots_kernel);
-        else if constexpr (std::is_same<V, float>::value)
-            kernel = SPMV_C16_PICK(csr_compact_scaled_dots_kernel);
-        else
-            kernel = SPMV_C16_PICK(csr_compact_f64_scaled_dots_kernel);
-#undef SPMV_C16_PICK
-        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
-                           scale->alpha, scale->beta, scale->y_in, d_y, static_cast<const T *>(dots->w), static_cast<spmv::v2d *>(dots->work), exact);
-        HIP_TRY(hipGetLastError());
-        return dots_reduce(*dots, pl->ntiles, s);
-    }
-    if (scale) {
-        const bool beta0 = scale->beta == 0.0;
-        void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, double, double,
-                       const T *, T *, int);
-#define SPMV_C16_PICK(NAME) (x32 ? (beta0 ? spmv::NAME<true, true> : spmv::NAME<true, false>) : (beta0 ? spmv::NAME<false, true> : spmv::NAME<false, false>))
-        if constexpr (std::is_same<T, float>::value)
-            kernel = SPMV_C16_PICK(csr_compact_f32xy_scaled_kernel);
-        else if constexpr (std::is_same<V, float>::value)
-            kernel = SPMV_C16_PICK(csr_compact_scaled_kernel);
-        else
-            kernel = SPMV_C16_PICK(csr_compact_f64_scaled_kernel);
-#undef SPMV_C16_PICK
-        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
-                           scale->alpha, scale->beta, scale->y_in, d_y, exact);
-        HIP_TRY(hipGetLastError());
-        return SPMV_HIP_OK;
-    }
-    void (*kernel)(int, const int4 *, const int *, const uint16_t *, const int32_t *, const int32_t *, const V *, const T *, T *, int);
-    if constexpr (std::is_same<T, float>::value)
-        kernel = x32 ? spmv::csr_compact_f32xy_kernel<true> : spmv::csr_compact_f32xy_kernel<false>;
-    else if constexpr (std::is_same<V, float>::value)
-        kernel = x32 ? spmv::csr_compact_kernel<true> : spmv::csr_compact_kernel<false>;
-    else
-        kernel = x32 ? spmv::csr_compact_f64_kernel<true> : spmv::csr_compact_f64_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, pl->d_bases, pl->d_codes, d_row_ptr, d_column_index, d_value, d_x,
-                       d_y, exact);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    return tile_multiply(C16Family<V, T>{pl}, d_row_ptr, d_column_index, d_value, d_x, d_y, stream, scale, dots);
 }
 
-// spmv_hip_upload_csr_compact (format 8) and spmv_hip_upload_csr_compact_f32xy (format 10: float_vectors)
-int upload_compact_floats(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr, const int32_t * column_index,
-                          const double * value, int allow_rounding, bool float_vectors)
+// ctx_tile_multiply once the format has chosen the plan, the value array and the vector pair: in place on y, w = x where A is square
+template <class Plan, class V, class T>
+int ctx_multiply(const spmv_hip_ctx * c, const Plan * pl, const V * value, const T * x, T * y, const double * ab, bool with_dots)
 {
-    if (!c)
-        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
-    if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "the compact multiply runs on one device (a context of spmv_hip_create)");
-    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
+    const ScaledArgs<T> scale{ab ? ab[0] : 0.0, ab ? ab[1] : 0.0, y}, *sp = ab ? &scale : nullptr;
+    const DotsArgs dots{c->rows == c->cols ? x : nullptr, c->d_dots, with_dots ? c->d_dots + 2 : nullptr, c->dots_work_bytes},
+        *dp = with_dots ? &dots : nullptr;
+    if constexpr (std::is_same<Plan, spmv_hip_f32_plan>::value)
+        return f32_multiply(pl, c->d_ptr, c->d_col, value, x, y, c->stream, sp, dp);
+    else
+        return c16_multiply(pl, c->d_ptr, c->d_col, value, x, y, c->stream, sp, dp);
+}
+
+} // namespace
+
+namespace spmvi {
+
+int ctx_tile_multiply(spmv_hip_ctx * c, const double * scale, bool with_dots)
+{
+    switch (c->format) {
+    case 7: return ctx_multiply(c, c->f32_plan, c->d_val32, c->d_x, c->d_y, scale, with_dots);
+    case 8: return ctx_multiply(c, c->c16_plan, c->d_val32, c->d_x, c->d_y, scale, with_dots);
+    case 9: return ctx_multiply(c, c->c16_plan, c->d_val, c->d_x, c->d_y, scale, with_dots);
+    case 10: return ctx_multiply(c, c->c16_plan, c->d_val32, c->d_x32, c->d_y32, scale, with_dots);
+    }
+    return fail(SPMV_HIP_ERR_STATE, "the context holds none of the formats 7 to 10");
+}
+
+int upload_float_tile(spmv_hip_ctx * c, int format, const char * multi, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
+                      const int32_t * column_index, const double * value, bool narrow_values, int allow_rounding, bool float_vectors)
+{
+    int rc = upload_csr_prelude(c, multi, nullptr, rows, cols, nnz, row_ptr, column_index, value);
+    if (rc != 0)
+        return rc;
     const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
     // everything that can refuse the matrix happens before anything is freed or copied
-    int rc = f32_check_host(rows, cols, row_ptr, flags);
-    if (rc != 0)
+    if ((rc = f32_check_host(rows, cols, row_ptr, flags)) != 0)
         return rc;
     if (row_ptr[rows] != nnz)
         return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
+    const bool f32 = format == 7;
+    F32HostPlan fp;
     HostPlan hp;
-    if ((rc = plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0) // (... the columns here)
-        return rc;
+    if ((rc = f32 ? check_columns(nnz, column_index, cols) : plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0)
+        return rc; // (the columns: the compact plan looks at them itself)
     std::vector<float> narrow;
-    try {
-        narrow.resize((size_t) nnz);
-    } catch (std::bad_alloc const &) {
-        return fail(SPMV_HIP_ERR_ALLOC, "compact upload: host memory");
+    if (narrow_values) {
+        try {
+            narrow.resize((size_t) nnz);
+        } catch (std::bad_alloc const &) {
+            return fail(SPMV_HIP_ERR_ALLOC, f32 ? "fp32-value upload: host memory" : "compact upload: host memory");
+        }
+        if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
+            return rc;
     }
-    if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
+    if (f32 && (rc = f32_plan_host_guarded(fp, rows, cols, row_ptr, flags, "fp32-value upload: host memory")) != 0)
         return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_ctx_matrix(c);
-    if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
+    if ((rc = f32 ? f32_build_plan(&c->f32_plan, fp, c->stream) : build_plan(&c->c16_plan, hp, c->stream)) != 0)
         return rc;
-    // only wide tiles read 32-bit columns
-    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr,
-                             column_index, c->c16_plan->wide_tiles > 0, narrow.data(), true, float_vectors)) != 0)
+    // the values narrowed (d_val32) or as they are (d_val); of the compact plans only wide tiles read 32-bit columns
+    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr, column_index,
+                             f32 || c->c16_plan->wide_tiles > 0, narrow_values ? (const void *) narrow.data() : value, narrow_values,
+                             float_vectors)) != 0)
         return rc;
     c->rows = rows;
     c->cols = cols;
     c->nnz = nnz;
-    c->bytes += c->c16_plan->device_bytes;
-    c->format = float_vectors ? 10 : 8;
+    c->bytes += f32 ? c->f32_plan->device_bytes : c->c16_plan->device_bytes;
+    c->format = format;
     return SPMV_HIP_OK;
 }
 
-} // namespace
+} // namespace spmvi
 
 extern "C" {
 
@@ -372,10 +359,7 @@ int spmv_hip_c16_plan_preview(int32_t rows, int32_t cols, const int32_t * host_r
             return fail(SPMV_HIP_ERR_INVALID, "tile_table is too small: it takes 13 int32 values per tile");
         for (int w = 0; w < nt; ++w) {
             int32_t * t = tile_table + (size_t) SPMV_HIP_C16_TILE_INTS * w;
-            t[0] = hp.desc[(size_t) w].x;
-            t[1] = hp.desc[(size_t) w].y;
-            t[2] = hp.desc[(size_t) w + 1].x - hp.desc[(size_t) w].x;
-            t[3] = (hp.desc[(size_t) w].z >> spmv::kTileMetaLanesShift) & 7;
+            tile_table_row(t, &hp.desc[(size_t) w]);
             t[4] = hp.windows[(size_t) w];
             for (int b = 0; b < 8; ++b)
                 t[5 + b] = t[4] ? hp.bases[8 * (size_t) w + b] : 0;
@@ -529,52 +513,24 @@ void spmv_hip_c16_plan_destroy(spmv_hip_c16_plan * pl)
 
 // ---- Level 1 --------------------------------------------------------------------------------------------------------------------
 
+static const char kCompactOneDevice[] = "the compact multiply runs on one device (a context of spmv_hip_create)";
+
 int spmv_hip_upload_csr_compact(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
                                 const int32_t * column_index, const double * value, int allow_rounding)
 {
-    return upload_compact_floats(c, rows, cols, nnz, row_ptr, column_index, value, allow_rounding, false);
+    return upload_float_tile(c, 8, kCompactOneDevice, rows, cols, nnz, row_ptr, column_index, value, true, allow_rounding, false);
 }
 
 int spmv_hip_upload_csr_compact_f32xy(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
                                       const int32_t * column_index, const double * value, int allow_rounding)
 {
-    return upload_compact_floats(c, rows, cols, nnz, row_ptr, column_index, value, allow_rounding, true);
+    return upload_float_tile(c, 10, kCompactOneDevice, rows, cols, nnz, row_ptr, column_index, value, true, allow_rounding, true);
 }
 
 int spmv_hip_upload_csr_compact_f64(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
                                     const int32_t * column_index, const double * value)
 {
-    if (!c)
-        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
-    if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "the compact multiply runs on one device (a context of spmv_hip_create)");
-    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
-    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
-    // everything that can refuse the matrix happens before anything is freed or copied
-    int rc = f32_check_host(rows, cols, row_ptr, flags);
-    if (rc != 0)
-        return rc;
-    if (row_ptr[rows] != nnz)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
-    HostPlan hp;
-    if ((rc = plan_host_guarded(hp, rows, cols, row_ptr, column_index, flags)) != 0) // (... the columns here)
-        return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_ctx_matrix(c);
-    if ((rc = build_plan(&c->c16_plan, hp, c->stream)) != 0)
-        return rc;
-    // the values as they are (d_val); only wide tiles read 32-bit columns
-    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr,
-                             column_index, c->c16_plan->wide_tiles > 0, value, false)) != 0)
-        return rc;
-    c->rows = rows;
-    c->cols = cols;
-    c->nnz = nnz;
-    c->bytes += c->c16_plan->device_bytes;
-    c->format = 9;
-    return SPMV_HIP_OK;
+    return upload_float_tile(c, 9, kCompactOneDevice, rows, cols, nnz, row_ptr, column_index, value, false, 0, false);
 }
 
 } // extern "C"

@@ -861,10 +861,7 @@ int spmv_hip_run(spmv_hip_ctx * c)
     case 1: rc = csr_run(); break;
     case 5: rc = spmv_hip_csr_symv(c->sym_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
     case 6: rc = spmv_hip_csr_spmv_t(c->tr_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
-    case 7: rc = spmv_hip_csr_spmv_f32(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
-    case 8: rc = spmv_hip_csr_spmv_c16(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, c->d_y, c->stream); break;
-    case 9: rc = spmv_hip_csr_spmv_c16_f64(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, c->d_y, c->stream); break;
-    case 10: rc = spmv_hip_csr_spmv_c16_f32xy(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, c->d_y32, c->stream); break;
+    case 7: case 8: case 9: case 10: rc = ctx_tile_multiply(c, nullptr, false); break;
     case 2:
         rc = c->as_csr ? csr_run() : ctx_coo_run(c, c->nnz, c->d_idx, c->d_col, c->d_val);
         break;
@@ -922,26 +919,8 @@ static int run_scaled(spmv_hip_ctx * c, double alpha, double beta, bool with_dot
     const bool timed = !(c->flags & SPMV_HIP_FLAG_NO_RUN_EVENTS);
     if (timed)
         HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    int rc = SPMV_HIP_OK;
-    if (with_dots) {
-        const bool square = c->rows == c->cols;
-        double * dots = c->d_dots;
-        void * work = c->d_dots + 2;
-        const size_t wb = c->dots_work_bytes;
-        switch (c->format) {
-        case 7: rc = spmv_hip_csr_spmv_f32_scaled_dots(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, square ? c->d_x : nullptr, dots, work, wb, c->stream); break;
-        case 8: rc = spmv_hip_csr_spmv_c16_scaled_dots(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, square ? c->d_x : nullptr, dots, work, wb, c->stream); break;
-        case 9: rc = spmv_hip_csr_spmv_c16_f64_scaled_dots(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, alpha, beta, c->d_y, c->d_y, square ? c->d_x : nullptr, dots, work, wb, c->stream); break;
-        default: rc = spmv_hip_csr_spmv_c16_f32xy_scaled_dots(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, alpha, beta, c->d_y32, c->d_y32, square ? c->d_x32 : nullptr, dots, work, wb, c->stream); break;
-        }
-    } else {
-        switch (c->format) {
-        case 7: rc = spmv_hip_csr_spmv_f32_scaled(c->f32_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
-        case 8: rc = spmv_hip_csr_spmv_c16_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
-        case 9: rc = spmv_hip_csr_spmv_c16_f64_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val, c->d_x, alpha, beta, c->d_y, c->d_y, c->stream); break;
-        default: rc = spmv_hip_csr_spmv_c16_f32xy_scaled(c->c16_plan, c->d_ptr, c->d_col, c->d_val32, c->d_x32, alpha, beta, c->d_y32, c->d_y32, c->stream); break;
-        }
-    }
+    const double scale[2] = {alpha, beta};
+    const int rc = ctx_tile_multiply(c, scale, with_dots);
     if (rc != 0)
         return rc;
     if (timed) {

@@ -1,5 +1,7 @@
-// f32_plan.hpp -- what compact.hip takes from f32values.hip: the tiling rule of the fp32-value multiplies (one rule: the compact
-// plan's descriptors ARE the fp32-value plan's, with its own bits added) and the narrowing of the values to float.
+// f32_plan.hpp -- what compact.hip and the Krylov files take from f32values.hip: the tiling rule of the fp32-value multiplies (one
+// rule: the compact plan's descriptors ARE the fp32-value plan's, with its own bits added), the narrowing of the values to float,
+// the checks and the tile-free path of the scaled multiplies and their dots (the ladder that calls them is tile_front.hpp's), and
+// the two Level-1 entries of formats 7 to 10 that compact.hip defines for both plans.
 #pragma once
 
 #include "internal.hpp"
@@ -25,6 +27,16 @@ struct F32HostPlan {
 int f32_check_host(int32_t rows, int32_t cols, const int32_t * row_ptr, unsigned flags);
 // the tiles of checked arguments; throws std::bad_alloc
 void f32_plan_host(F32HostPlan & hp, int32_t rows, int32_t cols, const int32_t * row_ptr, unsigned flags);
+// the two in one call that throws nothing: what the preview, the plan and the upload use (each with its own text for bad_alloc)
+int f32_plan_host_guarded(F32HostPlan & hp, int32_t rows, int32_t cols, const int32_t * row_ptr, unsigned flags,
+                          const char * out_of_memory = "fp32-value plan: host memory");
+// the host plan onto the current device
+int f32_build_plan(spmv_hip_f32_plan ** out, F32HostPlan const & hp, hipStream_t s);
+// every column in [0, cols)
+int check_columns(int32_t nnz, const int32_t * column_index, int32_t cols);
+// the four ints that open a tile-table row of either preview (first row, first entry, rows, log2 lanes per row) from the tile's
+// descriptor d[0] and the next one
+void tile_table_row(int32_t * t, const int4 * d);
 
 struct NarrowResult {
     long long inexact = 0, overflow = 0, first_inexact = -1, first_overflow = -1;
@@ -77,5 +89,16 @@ int dots_reduce(const DotsArgs & d, int n, hipStream_t s);
 // scaled_rows_only with the dots of what it stores
 int scaled_rows_only_dots(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out,
                           const DotsArgs & d, hipStream_t s);
+
+// spmv_hip_csr_spmv_f32 and its scaled forms (scale, dots: null, or as for tile_front.hpp's tile_multiply)
+int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                 const double * d_x, double * d_y, void * stream, const ScaledArgs<double> * scale, const DotsArgs * dots);
+
+// ---- Level 1 of formats 7 to 10 (compact.hip, beside internal.hpp's ctx_tile_multiply) ------------------------------------------------
+
+// The upload of `format`: the values narrowed to float (allow_rounding as in spmv_hip_f32values.h) or kept as doubles, x and y
+// doubles or floats; `multi` is what a multi-GPU context is told.  Refuses before anything of the previous matrix is freed.
+int upload_float_tile(spmv_hip_ctx * c, int format, const char * multi, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
+                      const int32_t * column_index, const double * value, bool narrow_values, int allow_rounding, bool float_vectors);
 
 } // namespace spmvi

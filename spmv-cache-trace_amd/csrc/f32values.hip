@@ -1,7 +1,9 @@
 // f32values.hip -- include/spmv_hip_f32values.h: y += fl32(A) x with the values stored and streamed as 4-byte floats.  The plan
 // cuts the rows into wave tiles on the host from row_ptr alone (the plain tiles of plan_csr.hip: lanes per row from the tile's
-// longest row, at most 16 entries per lane); the kernel is csr_f32values.hpp.
-#include "f32_plan.hpp"
+// longest row, at most 16 entries per lane); the kernel is csr_f32values.hpp.  The multiply's refusals and launches are
+// tile_front.hpp's: this file describes the family to it (F32Family) and defines what f32_plan.hpp declares for compact.hip,
+// whose upload_float_tile is the Level-1 upload of this format too.
+#include "tile_front.hpp"
 #include "csr_dots.hpp"
 
 #include <algorithm>
@@ -30,8 +32,79 @@ void plan_numbers(const spmv_hip_f32_plan & pl, int64_t * out, int n)
         out[i] = v[i];
 }
 
-// the host plan onto the current device
-int build_plan(spmv_hip_f32_plan ** out, F32HostPlan const & hp, hipStream_t s)
+int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_err)
+{
+    if (c.overflow > 0) {
+        char text[160];
+        std::snprintf(text, sizeof text, "%lld finite value(s) are infinite as floats (the first is entry %lld)", c.overflow, c.first_overflow);
+        return fail(SPMV_HIP_ERR_OVERFLOW, text);
+    }
+    if (inexact)
+        *inexact = c.inexact;
+    if (max_rel_err)
+        *max_rel_err = c.max_rel;
+    return SPMV_HIP_OK;
+}
+
+// csr_f32values.hpp's kernels take the descriptors alone in front of the arrays; a null column array is one more null pointer
+struct F32Family {
+    const spmv_hip_f32_plan * pl;
+    static const char * null_columns() { return nullptr; }
+    static bool columns_read() { return true; }
+    static auto plain(bool x32) { return with_bools([](auto X) { return spmv::csr_f32values_kernel<X()>; }, x32); }
+    static auto scaled(bool x32, bool b0) { return with_bools([](auto X, auto B0) { return spmv::csr_f32values_scaled_kernel<X(), B0()>; }, x32, b0); }
+    static auto dots(bool b0, bool w) { return with_bools([](auto B0, auto W) { return spmv::csr_f32values_scaled_dots_kernel<B0(), W()>; }, b0, w); }
+    template <class K, class... A>
+    void launch(K kernel, dim3 grid, hipStream_t s, A... a) const
+    {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, pl->ntiles, pl->d_desc, a...);
+    }
+};
+
+// slots of the path without tiles (one per wave of scaled_rows_only_dots_kernel)
+long long row_slots(int32_t rows) { return ((long long) rows + 63) / 64; }
+
+// the vector kernel of a scaled call where no tile runs, over T; d: with the dots of what it stores
+template <class T>
+int rows_only(int32_t rows, bool zterm, double alpha, double beta, const T * y_in, T * y_out, const DotsArgs * d, hipStream_t s)
+{
+    const dim3 grid((unsigned) (((long long) rows + 255) / 256));
+    if (!d) {
+        hipLaunchKernelGGL(with_bools([](auto B0, auto Z) { return spmv::scaled_rows_only_kernel<T, B0(), Z()>; }, beta == 0.0, zterm), grid,
+                           dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out);
+        HIP_TRY(hipGetLastError());
+        return SPMV_HIP_OK;
+    }
+    hipLaunchKernelGGL(with_bools([](auto B0, auto Z, auto W) { return spmv::scaled_rows_only_dots_kernel<T, B0(), Z(), W()>; }, beta == 0.0, zterm,
+                                  d->w != nullptr),
+                       grid, dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out, static_cast<const T *>(d->w), static_cast<spmv::v2d *>(d->work));
+    HIP_TRY(hipGetLastError());
+    return dots_reduce(*d, (int) row_slots(rows), s);
+}
+
+} // namespace
+
+// ---- what compact.hip and krylov.hip share (f32_plan.hpp) ------------------------------------------------------------------------------------
+
+namespace spmvi {
+
+long long reduce_blocks(long long n) { return (n + spmv::kDotsChunk - 1) / spmv::kDotsChunk; }
+
+bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned long long bbytes)
+{
+    if (!a || !b || abytes == 0 || bbytes == 0)
+        return false;
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return p < q + bbytes && q < p + abytes;
+}
+
+int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
+                 const double * d_x, double * d_y, void * stream, const ScaledArgs<double> * scale, const DotsArgs * dots)
+{
+    return tile_multiply(F32Family{pl}, d_row_ptr, d_column_index, d_value, d_x, d_y, stream, scale, dots);
+}
+
+int f32_build_plan(spmv_hip_f32_plan ** out, F32HostPlan const & hp, hipStream_t s)
 {
     spmv_hip_f32_plan * pl = new (std::nothrow) spmv_hip_f32_plan(hp.numbers);
     if (!pl)
@@ -51,130 +124,33 @@ int build_plan(spmv_hip_f32_plan ** out, F32HostPlan const & hp, hipStream_t s)
     return SPMV_HIP_OK;
 }
 
-int narrow_report(NarrowResult const & c, int64_t * inexact, double * max_rel_err)
+int f32_plan_host_guarded(F32HostPlan & hp, int32_t rows, int32_t cols, const int32_t * rp, unsigned flags, const char * out_of_memory)
 {
-    if (c.overflow > 0) {
-        char text[160];
-        std::snprintf(text, sizeof text, "%lld finite value(s) are infinite as floats (the first is entry %lld)", c.overflow, c.first_overflow);
-        return fail(SPMV_HIP_ERR_OVERFLOW, text);
+    const int rc = f32_check_host(rows, cols, rp, flags);
+    if (rc != 0)
+        return rc;
+    try {
+        f32_plan_host(hp, rows, cols, rp, flags);
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, out_of_memory);
     }
-    if (inexact)
-        *inexact = c.inexact;
-    if (max_rel_err)
-        *max_rel_err = c.max_rel;
     return SPMV_HIP_OK;
 }
 
-// spmv_hip_csr_spmv_f32 (scale null: y += fl32(A) x), spmv_hip_csr_spmv_f32_scaled (d_y is y_out) and, with dots,
-// spmv_hip_csr_spmv_f32_scaled_dots: one set of refusals
-int f32_multiply(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
-                 const double * d_x, double * d_y, void * stream, const ScaledArgs<double> * scale, const DotsArgs * dots = nullptr)
+int check_columns(int32_t nnz, const int32_t * col, int32_t cols)
 {
-    if (!pl)
-        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
-    if (d_x && (const void *) d_x == (const void *) d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "d_x and d_y must be different arrays");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (scale) {
-        int rc = scaled_vectors_check(pl->rows, sizeof(double), scale->beta, scale->y_in, d_y);
-        if (rc == 0 && dots)
-            rc = dots_check(*dots, pl->ntiles, pl->rows, pl->cols, pl->nnz, sizeof(double), sizeof(float), d_row_ptr, d_column_index, d_value, d_x,
-                            scale->beta, scale->y_in, d_y);
-        if (rc != 0)
-            return rc;
-        if (pl->rows == 0)
-            return dots ? dots_reduce(*dots, 0, s) : SPMV_HIP_OK;
-        if (scale->alpha == 0.0 || pl->ntiles == 0) { // the beta part alone: neither the matrix nor x is read
-            if (dots)
-                return scaled_rows_only_dots(pl->rows, false, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, *dots, s);
-            return scaled_rows_only(pl->rows, false, scale->alpha != 0.0, scale->alpha, scale->beta, scale->y_in, d_y, s);
-        }
-    }
-    if (pl->ntiles == 0) // rows, cols or nnz of zero
-        return SPMV_HIP_OK;
-    if (!d_row_ptr || !d_column_index || !d_value || !d_x || !d_y)
-        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
-    if (!aligned16(d_column_index) || !aligned16(d_value))
-        return fail(SPMV_HIP_ERR_ALIGN, "column / value arrays must be 16-byte aligned");
-    const dim3 grid((unsigned) ((pl->ntiles + 3) / 4)), block(256);
-    const int exact = (pl->flags & SPMV_HIP_FLAG_EXACT_ORDER) ? 1 : 0;
-    const bool x32 = (long long) pl->cols * 8 < (1LL << 32);
-    if (dots) { // (x32 holds: dots_check)
-        const bool beta0 = scale->beta == 0.0, hasw = dots->w != nullptr;
-        void (*kernel)(int, const int4 *, const int32_t *, const int32_t *, const float *, const double *, double, double, const double *, double *,
-                       const double *, spmv::v2d *, int);
-        if (beta0)
-            kernel = hasw ? spmv::csr_f32values_scaled_dots_kernel<true, true> : spmv::csr_f32values_scaled_dots_kernel<true, false>;
-        else
-            kernel = hasw ? spmv::csr_f32values_scaled_dots_kernel<false, true> : spmv::csr_f32values_scaled_dots_kernel<false, false>;
-        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, scale->alpha, scale->beta,
-                           scale->y_in, d_y, static_cast<const double *>(dots->w), static_cast<spmv::v2d *>(dots->work), exact);
-        HIP_TRY(hipGetLastError());
-        return dots_reduce(*dots, pl->ntiles, s);
-    }
-    if (scale) {
-        void (*kernel)(int, const int4 *, const int32_t *, const int32_t *, const float *, const double *, double, double, const double *, double *, int);
-        if (scale->beta == 0.0)
-            kernel = x32 ? spmv::csr_f32values_scaled_kernel<true, true> : spmv::csr_f32values_scaled_kernel<false, true>;
-        else
-            kernel = x32 ? spmv::csr_f32values_scaled_kernel<true, false> : spmv::csr_f32values_scaled_kernel<false, false>;
-        hipLaunchKernelGGL(kernel, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, scale->alpha, scale->beta,
-                           scale->y_in, d_y, exact);
-    } else if (x32)
-        hipLaunchKernelGGL(spmv::csr_f32values_kernel<true>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
-    else
-        hipLaunchKernelGGL(spmv::csr_f32values_kernel<false>, grid, block, 0, s, pl->ntiles, pl->d_desc, d_row_ptr, d_column_index, d_value, d_x, d_y, exact);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
+    bool bad = false;
+    for (int32_t e = 0; e < nnz; ++e)
+        bad |= col[e] < 0 || col[e] >= cols;
+    return bad ? fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)") : SPMV_HIP_OK;
 }
 
-template <class T>
-int rows_only(int32_t rows, bool zterm, double alpha, double beta, const T * y_in, T * y_out, hipStream_t s)
+void tile_table_row(int32_t * t, const int4 * d)
 {
-    void (*kernel)(int, double, double, const T *, T *);
-    if (beta == 0.0)
-        kernel = zterm ? spmv::scaled_rows_only_kernel<T, true, true> : spmv::scaled_rows_only_kernel<T, true, false>;
-    else
-        kernel = zterm ? spmv::scaled_rows_only_kernel<T, false, true> : spmv::scaled_rows_only_kernel<T, false, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned) (((long long) rows + 255) / 256)), dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out);
-    HIP_TRY(hipGetLastError());
-    return SPMV_HIP_OK;
-}
-
-// slots of the path without tiles (one per wave of scaled_rows_only_dots_kernel)
-long long row_slots(int32_t rows) { return ((long long) rows + 63) / 64; }
-
-template <class T>
-int rows_only_dots(int32_t rows, bool zterm, double alpha, double beta, const T * y_in, T * y_out, const DotsArgs & d, hipStream_t s)
-{
-    void (*kernel)(int, double, double, const T *, T *, const T *, spmv::v2d *);
-    const bool beta0 = beta == 0.0, hasw = d.w != nullptr;
-#define SPMV_ROWS_PICK(B, Z) (hasw ? spmv::scaled_rows_only_dots_kernel<T, B, Z, true> : spmv::scaled_rows_only_dots_kernel<T, B, Z, false>)
-    if (beta0)
-        kernel = zterm ? SPMV_ROWS_PICK(true, true) : SPMV_ROWS_PICK(true, false);
-    else
-        kernel = zterm ? SPMV_ROWS_PICK(false, true) : SPMV_ROWS_PICK(false, false);
-#undef SPMV_ROWS_PICK
-    hipLaunchKernelGGL(kernel, dim3((unsigned) (((long long) rows + 255) / 256)), dim3(256), 0, s, (int) rows, alpha, beta, y_in, y_out,
-                       static_cast<const T *>(d.w), static_cast<spmv::v2d *>(d.work));
-    HIP_TRY(hipGetLastError());
-    return dots_reduce(d, (int) row_slots(rows), s);
-}
-
-} // namespace
-
-// ---- what compact.hip and krylov.hip share (f32_plan.hpp) ------------------------------------------------------------------------------------
-
-namespace spmvi {
-
-long long reduce_blocks(long long n) { return (n + spmv::kDotsChunk - 1) / spmv::kDotsChunk; }
-
-bool overlap(const void * a, unsigned long long abytes, const void * b, unsigned long long bbytes)
-{
-    if (!a || !b || abytes == 0 || bbytes == 0)
-        return false;
-    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-    return p < q + bbytes && q < p + abytes;
+    t[0] = d[0].x;
+    t[1] = d[0].y;
+    t[2] = d[1].x - d[0].x;
+    t[3] = (d[0].z >> spmv::kTileMetaLanesShift) & 7;
 }
 
 int f32_check_host(int32_t rows, int32_t cols, const int32_t * rp, unsigned flags)
@@ -299,16 +275,16 @@ int scaled_vectors_check(int32_t rows, size_t elem, double beta, const void * y_
 int scaled_rows_only(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out, hipStream_t s)
 {
     if (float_vectors)
-        return rows_only(rows, zterm, alpha, beta, static_cast<const float *>(y_in), static_cast<float *>(y_out), s);
-    return rows_only(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), s);
+        return rows_only(rows, zterm, alpha, beta, static_cast<const float *>(y_in), static_cast<float *>(y_out), nullptr, s);
+    return rows_only(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), nullptr, s);
 }
 
 int scaled_rows_only_dots(int32_t rows, bool float_vectors, bool zterm, double alpha, double beta, const void * y_in, void * y_out,
                           const DotsArgs & d, hipStream_t s)
 {
     if (float_vectors)
-        return rows_only_dots(rows, zterm, alpha, beta, static_cast<const float *>(y_in), static_cast<float *>(y_out), d, s);
-    return rows_only_dots(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), d, s);
+        return rows_only(rows, zterm, alpha, beta, static_cast<const float *>(y_in), static_cast<float *>(y_out), &d, s);
+    return rows_only(rows, zterm, alpha, beta, static_cast<const double *>(y_in), static_cast<double *>(y_out), &d, s);
 }
 
 size_t dots_workspace_bytes(int ntiles, int32_t rows)
@@ -431,25 +407,16 @@ int spmv_hip_f32_plan_preview(int32_t rows, int32_t cols, const int32_t * host_r
 {
     if (!out || n < 0 || tile_table_ints < 0)
         return fail(SPMV_HIP_ERR_INVALID, "out is null, or a negative count");
-    int rc;
-    if ((rc = f32_check_host(rows, cols, host_row_ptr, flags)) != 0)
-        return rc;
     F32HostPlan hp;
-    try {
-        f32_plan_host(hp, rows, cols, host_row_ptr, flags);
-    } catch (std::bad_alloc const &) {
-        return fail(SPMV_HIP_ERR_ALLOC, "fp32-value plan: host memory");
-    }
+    const int rc = f32_plan_host_guarded(hp, rows, cols, host_row_ptr, flags);
+    if (rc != 0)
+        return rc;
     const int nt = hp.numbers.ntiles;
     if (tile_table) {
         if (4LL * nt > tile_table_ints)
             return fail(SPMV_HIP_ERR_INVALID, "tile_table is too small: it takes 4 int32 values per tile");
-        for (int w = 0; w < nt; ++w) {
-            tile_table[4 * w] = hp.desc[(size_t) w].x;
-            tile_table[4 * w + 1] = hp.desc[(size_t) w].y;
-            tile_table[4 * w + 2] = hp.desc[(size_t) w + 1].x - hp.desc[(size_t) w].x;
-            tile_table[4 * w + 3] = (hp.desc[(size_t) w].z >> spmv::kTileMetaLanesShift) & 7;
-        }
+        for (int w = 0; w < nt; ++w)
+            tile_table_row(tile_table + 4 * (size_t) w, &hp.desc[(size_t) w]);
     }
     plan_numbers(hp.numbers, out, n);
     return SPMV_HIP_OK;
@@ -461,25 +428,20 @@ int spmv_hip_f32_plan_csr(spmv_hip_f32_plan ** plan, int32_t rows, int32_t cols,
     if (!plan)
         return fail(SPMV_HIP_ERR_INVALID, "plan is null");
     *plan = nullptr;
-    int rc;
-    if ((rc = f32_check_host(rows, cols, host_row_ptr, flags)) != 0)
-        return rc;
     F32HostPlan hp;
-    try {
-        f32_plan_host(hp, rows, cols, host_row_ptr, flags);
-    } catch (std::bad_alloc const &) {
-        return fail(SPMV_HIP_ERR_ALLOC, "fp32-value plan: host memory");
-    }
+    const int rc = f32_plan_host_guarded(hp, rows, cols, host_row_ptr, flags);
+    if (rc != 0)
+        return rc;
     int devices = 0;
     if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1)
         return fail(SPMV_HIP_ERR_NO_DEVICE, "no HIP device visible");
-    return build_plan(plan, hp, static_cast<hipStream_t>(stream));
+    return f32_build_plan(plan, hp, static_cast<hipStream_t>(stream));
 }
 
 int spmv_hip_csr_spmv_f32(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
                           const float * d_value, const double * d_x, double * d_y, void * stream)
 {
-    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream, nullptr);
+    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y, stream, nullptr, nullptr);
 }
 
 int spmv_hip_csr_spmv_f32_scaled(const spmv_hip_f32_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index,
@@ -487,7 +449,7 @@ int spmv_hip_csr_spmv_f32_scaled(const spmv_hip_f32_plan * pl, const int32_t * d
                                  double * d_y_out, void * stream)
 {
     const ScaledArgs<double> scale{alpha, beta, d_y_in};
-    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale);
+    return f32_multiply(pl, d_row_ptr, d_column_index, d_value, d_x, d_y_out, stream, &scale, nullptr);
 }
 
 int spmv_hip_f32_plan_info(const spmv_hip_f32_plan * pl, int64_t * out, int n)
@@ -512,47 +474,8 @@ void spmv_hip_f32_plan_destroy(spmv_hip_f32_plan * pl)
 int spmv_hip_upload_csr_f32values(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
                                   const int32_t * column_index, const double * value, int allow_rounding)
 {
-    if (!c)
-        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
-    if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "the fp32-value multiply runs on one device (a context of spmv_hip_create)");
-    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
-    const unsigned flags = c->flags & SPMV_HIP_FLAG_EXACT_ORDER;
-    int rc = f32_check_host(rows, cols, row_ptr, flags);
-    if (rc != 0)
-        return rc;
-    if (row_ptr[rows] != nnz)
-        return fail(SPMV_HIP_ERR_INVALID, "row_ptr[rows] must equal nnz");
-    bool bad = false;
-    for (int32_t e = 0; e < nnz; ++e)
-        bad |= column_index[e] < 0 || column_index[e] >= cols;
-    if (bad)
-        return fail(SPMV_HIP_ERR_INVALID, "column index out of range [0, cols)");
-    // everything that can refuse the matrix happens before anything is freed or copied
-    std::vector<float> narrow;
-    F32HostPlan hp;
-    try {
-        narrow.resize((size_t) nnz);
-        if ((rc = narrow_refusal(narrow_host(nnz, value, narrow.data()), allow_rounding)) != 0)
-            return rc;
-        f32_plan_host(hp, rows, cols, row_ptr, flags);
-    } catch (std::bad_alloc const &) {
-        return fail(SPMV_HIP_ERR_ALLOC, "fp32-value upload: host memory");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_ctx_matrix(c);
-    if ((rc = build_plan(&c->f32_plan, hp, c->stream)) != 0)
-        return rc;
-    if ((rc = upload_ctx_csr(c, (size_t) rows + 1, (size_t) cols, (size_t) rows, (size_t) nnz, row_ptr, column_index, true, narrow.data(), true)) != 0)
-        return rc;
-    c->rows = rows;
-    c->cols = cols;
-    c->nnz = nnz;
-    c->bytes += c->f32_plan->device_bytes;
-    c->format = 7;
-    return SPMV_HIP_OK;
+    return upload_float_tile(c, 7, "the fp32-value multiply runs on one device (a context of spmv_hip_create)", rows, cols, nnz, row_ptr, column_index,
+                             value, true, allow_rounding, false);
 }
 
 } // extern "C"

@@ -13,8 +13,9 @@
 //   f32values.hip    y += fl32(A) x with the values stored as 4-byte floats (spmv_hip_f32values.h)
 //   compact.hip      ... and the columns of a tile as 16-bit window codes (spmv_hip_compact.h)
 //   krylov.hip       the vector updates of a CG iteration with their scalars read from device memory (spmv_hip_krylov.h)
-// The last two share one tiling rule and the narrowing of the values (f32_plan.hpp, defined in f32values.hip) and one tile
-// kernel body over three column sources (csr_f32values.hpp: f32_tile; csr_compact.hpp adds the two code sources).
+// f32values.hip and compact.hip share one tiling rule and the narrowing of the values (f32_plan.hpp, defined in f32values.hip), one
+// tile kernel body over three column sources (csr_f32values.hpp: f32_tile; csr_compact.hpp adds the two code sources) and one
+// host front for their multiplies (tile_front.hpp).
 #pragma once
 
 #include "spmv_hip_plan.h"
@@ -316,6 +317,16 @@ void free_ctx_matrix(spmv_hip_ctx * c);
 // padded by 64 bytes and counted in c->bytes; synchronises.  On failure the matrix is freed and the first error text kept.
 int upload_ctx_csr(spmv_hip_ctx * c, size_t nptr, size_t nx, size_t ny, size_t nnz, const int32_t * row_ptr, const int32_t * column_index,
                    bool keep_columns, const void * value, bool float_values, bool float_vectors = false);
+
+// common.hip: what the Level-1 CSR uploads of formats 5 to 10 refuse first, in this order: a null context, a multi-GPU one
+// (`multi` is the family's sentence), SPMV_HIP_FLAG_EXACT_ORDER where the family cannot keep it (`exact` is its sentence, null
+// where it can), and "bad CSR arguments" (a negative size, row_ptr null, entries without columns or values)
+int upload_csr_prelude(const spmv_hip_ctx * c, const char * multi, const char * exact, int32_t rows, int32_t cols, int32_t nnz,
+                       const int32_t * row_ptr, const int32_t * column_index, const double * value);
+
+// compact.hip: one multiply of a context that holds format 7, 8, 9 or 10, on its own arrays and stream: y += A x (scale null),
+// y <- scale[0] A x + scale[1] y, or that with its two dots into c->d_dots (spmv_hip_run_scaled_dots)
+int ctx_tile_multiply(spmv_hip_ctx * c, const double * scale, bool with_dots);
 
 // multi_gpu.hip
 void multi_free_matrix(spmv_hip_ctx * c);

@@ -378,15 +378,11 @@ void spmv_hip_sym_plan_destroy(spmv_hip_sym_plan * pl)
 int spmv_hip_upload_csr_symmetric(spmv_hip_ctx * c, int32_t rows, int32_t nnz, const int32_t * row_ptr, const int32_t * column_index,
                                   const double * value, int kind)
 {
-    if (!c)
-        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
-    if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "a symmetric multiply runs on one device (spmv_hip_create_multi partitions rows)");
-    if (c->flags & SPMV_HIP_FLAG_EXACT_ORDER)
-        return fail(SPMV_HIP_ERR_INVALID, "SPMV_HIP_FLAG_EXACT_ORDER cannot be kept: a symmetric multiply adds partial sums with atomics");
-    if (rows < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
-    int rc = check_csr_host(rows, row_ptr);
+    int rc = upload_csr_prelude(c, "a symmetric multiply runs on one device (spmv_hip_create_multi partitions rows)",
+                                "SPMV_HIP_FLAG_EXACT_ORDER cannot be kept: a symmetric multiply adds partial sums with atomics", rows, rows, nnz,
+                                row_ptr, column_index, value);
+    if (rc == 0)
+        rc = check_csr_host(rows, row_ptr);
     if (rc != 0)
         return rc;
     if (row_ptr[rows] != nnz)

@@ -375,15 +375,11 @@ void spmv_hip_tr_plan_destroy(spmv_hip_tr_plan * pl)
 int spmv_hip_upload_csr_transposed(spmv_hip_ctx * c, int32_t rows, int32_t cols, int32_t nnz, const int32_t * row_ptr,
                                    const int32_t * column_index, const double * value)
 {
-    if (!c)
-        return fail(SPMV_HIP_ERR_INVALID, "ctx is null");
-    if (c->multi)
-        return fail(SPMV_HIP_ERR_STATE, "a transposed multiply runs on one device (a row partition would need a reduction of y across devices)");
-    if (c->flags & SPMV_HIP_FLAG_EXACT_ORDER)
-        return fail(SPMV_HIP_ERR_INVALID, "SPMV_HIP_FLAG_EXACT_ORDER cannot be kept: a transposed multiply adds its products with atomics");
-    if (rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!column_index || !value)))
-        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments");
-    int rc = check_csr_row_ptr(rows, cols, row_ptr);
+    int rc = upload_csr_prelude(c, "a transposed multiply runs on one device (a row partition would need a reduction of y across devices)",
+                                "SPMV_HIP_FLAG_EXACT_ORDER cannot be kept: a transposed multiply adds its products with atomics", rows, cols, nnz,
+                                row_ptr, column_index, value);
+    if (rc == 0)
+        rc = check_csr_row_ptr(rows, cols, row_ptr);
     if (rc != 0)
         return rc;
     if (row_ptr[rows] != nnz)
