@@ -1,5 +1,5 @@
 // krylov_stream.hpp -- the cut of a vector that every Krylov update kernel streams over (cg_updates.hpp, bicgstab_updates.hpp,
-// gmres_updates.hpp, bjacobi_kernels.hpp, cheby_updates.hpp), written once.  The kernels are shaped as triad_kernel is -- 16-byte loads and stores,
+// gmres_updates.hpp, bjacobi_kernels.hpp, cheby_updates.hpp, the dots pass of mcgs_kernels.hpp), written once.  The kernels are shaped as triad_kernel is -- 16-byte loads and stores,
 // several independent loads per lane in flight -- over a FIXED cut: chunk c = elements [c kKrylovChunk, (c + 1) kKrylovChunk)
 // belongs to wave c of the grid (four to a workgroup), and lane l of that wave takes the 16-byte groups l, l + 64, ... of the
 // chunk in that order.  Whole chunks run in unrolled passes of U groups per array without a bounds test; the last chunk of a

@@ -1,7 +1,7 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
-spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h and
-spmv_hip_cheby.h (the C ABI of libspmv_hip.so).
+spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h,
+spmv_hip_cheby.h and spmv_hip_mcgs.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -28,7 +28,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
                                           "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h",
-                                          "spmv_hip_cheby.h")]
+                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -209,6 +209,14 @@ SIGNATURES = {
     "spmv_hip_cheby_coeffs": (C.c_int, [C.c_int32, _vp, C.c_double, C.c_double, _vp, _vp]),
     "spmv_hip_cheby_step_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8 + [C.c_size_t, _vp]),
     "spmv_hip_cheby_step_f32": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8 + [C.c_size_t, _vp]),
+    # spmv_hip_mcgs.h
+    "spmv_hip_mcgs_workspace": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "spmv_hip_mcgs_colour": (C.c_int, [C.c_int32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_mcgs_permute": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_size_t, _vp]),
+    "spmv_hip_mcgs_sweep_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp, _vp]),
+    "spmv_hip_mcgs_sweep_f32": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp, _vp]),
+    "spmv_hip_mcgs_apply_f64": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_mcgs_apply_f32": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 
@@ -1280,3 +1288,64 @@ def cheby_step(n, degree, j, d_coef, d_u, d_minv, d_d, d_z, d_r=None, d_dots=Non
         work_bytes = d_work.numel() * d_work.element_size() if d_work is not None else 0
     check(fn(n, degree, j, _addr(d_coef), _addr(d_u), _addr(d_minv), _addr(d_d), _addr(d_z), _addr(d_r), _addr(d_dots), _addr(d_work),
              work_bytes, stream))
+
+
+MCGS_MAX_COLOURS = 64
+
+
+class McgsPlan(C.Structure):
+    """spmv_hip_mcgs_plan (include/spmv_hip_mcgs.h): every field public; the four device arrays are the caller's."""
+    _fields_ = [("rows", C.c_int32), ("colours", C.c_int32), ("conflicts", C.c_int32), ("group", C.c_int32),
+                ("colour_ptr", C.c_int32 * (MCGS_MAX_COLOURS + 1)), ("d_order", _vp), ("d_row_ptr", _vp), ("d_column_index", _vp),
+                ("d_value", _vp)]
+
+
+def _work_bytes(d_work, work_bytes):
+    if work_bytes is None:
+        return d_work.numel() * d_work.element_size() if d_work is not None else 0
+    return work_bytes
+
+
+def mcgs_workspace_bytes(rows):
+    """The workspace mcgs_colour and mcgs_permute need over `rows` rows: a function of rows alone, at least 16."""
+    b = C.c_size_t(0)
+    check(load().spmv_hip_mcgs_workspace(rows, C.byref(b)))
+    return b.value
+
+
+def mcgs_colour(rows, d_row_ptr, d_column_index, seed, d_colour, d_status, d_work, work_bytes=None, stream=0):
+    """d_colour (rows int32) <- the colours 0 ... 63 of the rows of the device CSR pattern, by Jones-Plassmann with first fit under
+    `seed`; d_status (four int32) <- {colours, rounds, conflicts, overflowed rows} (include/spmv_hip_mcgs.h).  Torch tensors or raw
+    device addresses; work_bytes defaults to the size of a tensor d_work.  SYNCHRONISES the stream."""
+    check(load().spmv_hip_mcgs_colour(rows, _addr(d_row_ptr), _addr(d_column_index), seed, _addr(d_colour), _addr(d_status), _addr(d_work),
+                                      _work_bytes(d_work, work_bytes), stream))
+
+
+def mcgs_permute(rows, nnz, d_row_ptr, d_column_index, d_value, d_colour, d_status, d_order, d_perm_row_ptr, d_perm_column_index, d_perm_value,
+                 d_work, work_bytes=None, stream=0):
+    """The colour-major plan: d_order (rows int32) <- the rows colour by colour, the three d_perm arrays (rows + 1, nnz, nnz) <- the
+    matrix with its rows in that order; returns the McgsPlan that points to them (keep the arrays alive).  Arguments as for
+    mcgs_colour.  SYNCHRONISES the stream."""
+    plan = McgsPlan()
+    check(load().spmv_hip_mcgs_permute(rows, nnz, _addr(d_row_ptr), _addr(d_column_index), _addr(d_value), _addr(d_colour), _addr(d_status),
+                                       _addr(d_order), _addr(d_perm_row_ptr), _addr(d_perm_column_index), _addr(d_perm_value), C.byref(plan),
+                                       _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+    return plan
+
+
+def _plan_ref(plan):
+    return None if plan is None else C.byref(plan)
+
+
+def mcgs_sweep(plan, first, last, omega, d_b, d_minv, d_x, stream=0, dtype=None):
+    """The SOR update x_i <- (1 - omega) x_i + omega minv_i (b_i - sum_{j != i} a_ij x_j) of the colours first ... last of the plan
+    (descending where last < first), x in place: one launch per colour.  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_mcgs_sweep_" + _krylov_suffix((d_b, d_minv, d_x), dtype))
+    check(fn(_plan_ref(plan), first, last, omega, _addr(d_b), _addr(d_minv), _addr(d_x), stream))
+
+
+def mcgs_apply(plan, omega, d_r, d_minv, d_z, d_dots=None, d_work=None, work_bytes=None, stream=0, dtype=None):
+    """z <- the SSOR operator of the plan applied to r (z zeroed, a sweep forwards, a sweep backwards) and, with d_dots and d_work
+    (krylov_workspace_bytes(rows)), d_dots <- {r' z, z' z} of z as stored.  Arguments as for bjacobi_apply.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_mcgs_apply_" + _krylov_suffix((d_r, d_minv, d_z), dtype))
+    check(fn(_plan_ref(plan), omega, _addr(d_r), _addr(d_minv), _addr(d_z), _addr(d_dots), _addr(d_work), _work_bytes(d_work, work_bytes), stream))
