@@ -12,35 +12,18 @@
 // addresses.  Every write of y is atomic: a later range's windows cover an earlier range's rows.  The order in which the partial
 // sums meet is not fixed, so y is not reproducible bit for bit (like the column panels of the general kernel).
 //
-// Entries are walked in quads: a lane loads four consecutive column indices (16 B) and values (2 x 16 B) at a quad-aligned entry,
-// exactly as they lie in the caller's arrays; the row of its first entry comes from a binary search in the range's row_ptr, kept
-// in LDS.  Columns outside [0, rows) are skipped (the plan refused them; a caller who changes the columns afterwards gets a
-// wrong y, never an access outside x, y or LDS).
+// The windows, the range's row_ptr in LDS, the walk over the entries in quads and the flush are window_walk.hpp, shared with
+// csr_transpose.hpp; the loop over a quad's entries below is this kernel's own.  Columns outside [0, rows) are skipped (the plan
+// refused them; a caller who changes the columns afterwards gets a wrong y, never an access outside x, y or LDS).
 #pragma once
 
-#include "tile_common.hpp"
+#include "window_walk.hpp"
 
 namespace spmv {
 
-constexpr int kSymBlock = 512;      // threads per workgroup
-constexpr int kSymMaxWindows = 8;   // the own window + at most 7 more
-constexpr int kSymQuadsPerLane = 2; // quads whose loads are in flight together per lane
-
-template <int KW>
-__device__ __forceinline__ int sym_slot(int j, int r0, int nr, const int (&wb)[KW > 0 ? KW : 1], const int (&wl)[KW > 0 ? KW : 1],
-                                        const int (&wo)[KW > 0 ? KW : 1])
-{
-    int slot = ((unsigned) (j - r0) < (unsigned) nr) ? j - r0 : -1;
-#pragma unroll
-    for (int w = 0; w < KW; ++w)
-        if (slot < 0 && (unsigned) (j - wb[w]) < (unsigned) wl[w])
-            slot = wo[w] + (j - wb[w]);
-    return slot;
-}
-
 // win: [ranges][stride] {first row, length} of the extra windows (length 0: unused), stride <= KW
 template <int KW>
-__global__ __launch_bounds__(kSymBlock, 2) void csr_symv_kernel(
+__global__ __launch_bounds__(kWinBlock, 2) void csr_symv_kernel(
     int rows, int R, const int32_t * __restrict__ p, const int32_t * __restrict__ col, const double * __restrict__ val,
     const double * __restrict__ x, double * __restrict__ y, const int2 * __restrict__ win, int stride, int slots, double tsign)
 {
@@ -48,66 +31,23 @@ __global__ __launch_bounds__(kSymBlock, 2) void csr_symv_kernel(
     int * rp = reinterpret_cast<int *>(sym_lds + slots);
     const int r0 = blockIdx.x * R;
     const int nr = min(R, rows - r0);
-    constexpr int KA = KW > 0 ? KW : 1;
-    int wb[KA], wl[KA], wo[KA];
-    int off = nr;
-#pragma unroll
-    for (int w = 0; w < KW; ++w) {
-        const int2 d = w < stride ? win[(size_t) blockIdx.x * stride + w] : make_int2(0, 0);
-        wb[w] = d.x;
-        wl[w] = d.y;
-        wo[w] = off;
-        off += d.y;
-    }
-    if (KW == 0)
-        wb[0] = wl[0] = wo[0] = 0;
-    const int used = off; // slots of this range (<= slots)
-    for (int t = threadIdx.x; t < used; t += kSymBlock)
-        sym_lds[t] = 0.0;
-    for (int t = threadIdx.x; t <= nr; t += kSymBlock)
-        rp[t] = p[r0 + t];
-    __syncthreads();
+    RangeWindows<KW> ws;
+    ws.load(win, stride, nr);
+    range_prologue(sym_lds, ws.used, rp, p, r0, nr);
     const long long eb = rp[0], ee = rp[nr];
 
-    for (long long q0 = (eb >> 2) + threadIdx.x; 4 * q0 < ee; q0 += (long long) kSymQuadsPerLane * kSymBlock) {
-        v4i c[kSymQuadsPerLane];
-        v2d a01[kSymQuadsPerLane], a23[kSymQuadsPerLane];
+    for (long long q0 = (eb >> 2) + threadIdx.x; 4 * q0 < ee; q0 += (long long) kWinQuadsPerLane * kWinBlock) {
+        v4i c[kWinQuadsPerLane];
+        v2d a01[kWinQuadsPerLane], a23[kWinQuadsPerLane];
 #pragma unroll
-        for (int u = 0; u < kSymQuadsPerLane; ++u) {
-            const long long e0 = 4 * (q0 + (long long) u * kSymBlock);
-            if (e0 >= eb && e0 + 3 < ee) {
-                c[u] = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(col + e0));
-                a01[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(val + e0));
-                a23[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(val + e0 + 2));
-            } else {
-                // the range's first and last quads: only the entries inside [eb, ee) are read; the others get column -1 (skipped)
-                double a[4];
+        for (int u = 0; u < kWinQuadsPerLane; ++u)
+            load_quad(4 * (q0 + (long long) u * kWinBlock), eb, ee, col, val, c[u], a01[u], a23[u]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const bool in = e0 + k >= eb && e0 + k < ee;
-                    c[u][k] = in ? col[e0 + k] : -1;
-                    a[k] = in ? val[e0 + k] : 0.0;
-                }
-                a01[u] = v2d{a[0], a[1]};
-                a23[u] = v2d{a[2], a[3]};
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSymQuadsPerLane; ++u) {
-            const long long e0 = 4 * (q0 + (long long) u * kSymBlock);
+        for (int u = 0; u < kWinQuadsPerLane; ++u) {
+            const long long e0 = 4 * (q0 + (long long) u * kWinBlock);
             if (e0 >= ee)
                 continue;
-            // the row of the quad's first entry inside the range: the last r with rp[r] <= max(e0, eb)
-            const long long ef = e0 > eb ? e0 : eb;
-            int lo = 0, hi = nr;
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (rp[mid] <= ef)
-                    lo = mid;
-                else
-                    hi = mid;
-            }
-            int r = lo;
+            int r = quad_first_row(rp, nr, e0, eb);
             double sum = 0.0;
             const double av[4] = {a01[u][0], a01[u][1], a23[u][0], a23[u][1]};
 #pragma unroll
@@ -129,7 +69,7 @@ __global__ __launch_bounds__(kSymBlock, 2) void csr_symv_kernel(
                 const int i = r0 + r;
                 if (j != i) {
                     const double t = (tsign * a) * x[i];
-                    const int slot = sym_slot<KW>(j, r0, nr, wb, wl, wo);
+                    const int slot = ws.slot_of(j, (unsigned) (j - r0) < (unsigned) nr ? j - r0 : -1);
                     if (slot >= 0)
                         atomicAdd(sym_lds + slot, t);
                     else
@@ -141,19 +81,13 @@ __global__ __launch_bounds__(kSymBlock, 2) void csr_symv_kernel(
         }
     }
     __syncthreads();
-    // flush: own rows, then every extra window; lanes on consecutive addresses, zero slots skipped
-    for (int t = threadIdx.x; t < nr; t += kSymBlock) {
+    // flush: own rows, then every extra window
+    for (int t = threadIdx.x; t < nr; t += kWinBlock) {
         const double v = sym_lds[t];
         if (v != 0.0)
             atomicAdd(y + r0 + t, v);
     }
-#pragma unroll
-    for (int w = 0; w < KW; ++w)
-        for (int t = threadIdx.x; t < wl[w]; t += kSymBlock) {
-            const double v = sym_lds[wo[w] + t];
-            if (v != 0.0)
-                atomicAdd(y + wb[w] + t, v);
-        }
+    ws.flush(sym_lds, y);
 }
 
 } // namespace spmv
