@@ -1,7 +1,7 @@
-// krylov_check.hpp -- what bicgstab.hip, gmres.hip, bjacobi.hip, cheby.hip and mcgs.hip take from krylov.hip: the workspace rule of a step's dots, the
+// krylov_check.hpp -- what bicgstab.hip, gmres.hip, bjacobi.hip, cheby.hip, mcgs.hip and agg.hip take from krylov.hip: the workspace rule of a step's dots, the
 // table-driven check of the arrays of one call and the launch over the chunk grid of krylov_stream.hpp
 // (include/spmv_hip_krylov.h, include/spmv_hip_bicgstab.h, include/spmv_hip_gmres.h, include/spmv_hip_bjacobi.h, include/spmv_hip_cheby.h,
-// include/spmv_hip_mcgs.h).
+// include/spmv_hip_mcgs.h, include/spmv_hip_agg.h).
 #pragma once
 
 #include "f32_plan.hpp"

@@ -1,7 +1,7 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
 spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h,
-spmv_hip_cheby.h and spmv_hip_mcgs.h (the C ABI of libspmv_hip.so).
+spmv_hip_cheby.h, spmv_hip_mcgs.h and spmv_hip_agg.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -28,7 +28,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
                                           "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h",
-                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h")]
+                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h", "spmv_hip_agg.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -217,6 +217,16 @@ SIGNATURES = {
     "spmv_hip_mcgs_sweep_f32": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp, _vp]),
     "spmv_hip_mcgs_apply_f64": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "spmv_hip_mcgs_apply_f32": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    # spmv_hip_agg.h
+    "spmv_hip_agg_workspace": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "spmv_hip_agg_aggregate": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_double, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_agg_plan": (C.c_int, [C.c_int32] + [_vp] * 6 + [C.c_size_t, _vp]),
+    "spmv_hip_agg_galerkin_symbolic": (C.c_int, [_vp, C.c_int32] + [_vp] * 8 + [C.c_size_t, _vp]),
+    "spmv_hip_agg_galerkin_numeric": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 5),
+    "spmv_hip_agg_restrict_f64": (C.c_int, [_vp] * 4),
+    "spmv_hip_agg_restrict_f32": (C.c_int, [_vp] * 4),
+    "spmv_hip_agg_prolong_add_f64": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp]),
+    "spmv_hip_agg_prolong_add_f32": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp]),
 }
 
 
@@ -1349,3 +1359,59 @@ def mcgs_apply(plan, omega, d_r, d_minv, d_z, d_dots=None, d_work=None, work_byt
     (krylov_workspace_bytes(rows)), d_dots <- {r' z, z' z} of z as stored.  Arguments as for bjacobi_apply.  Only enqueues."""
     fn = getattr(load(), "spmv_hip_mcgs_apply_" + _krylov_suffix((d_r, d_minv, d_z), dtype))
     check(fn(_plan_ref(plan), omega, _addr(d_r), _addr(d_minv), _addr(d_z), _addr(d_dots), _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+
+
+class AggPlan(C.Structure):
+    """struct spmv_hip_agg_plan (include/spmv_hip_agg.h): every field public; the three device arrays are the caller's."""
+    _fields_ = [("rows", C.c_int32), ("aggregates", C.c_int32), ("largest", C.c_int32), ("d_agg", _vp), ("d_member_ptr", _vp),
+                ("d_member", _vp)]
+
+
+def agg_workspace_bytes(rows, nnz=0):
+    """The workspace of agg_aggregate and agg_plan (nnz = 0) and of agg_galerkin_symbolic: a function of (rows, nnz) alone."""
+    b = C.c_size_t(0)
+    check(load().spmv_hip_agg_workspace(rows, nnz, C.byref(b)))
+    return b.value
+
+
+def agg_aggregate(rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes=None, stream=0):
+    """d_agg (rows int32) <- the aggregate of every row of the device CSR matrix under `seed`, a neighbour being a stored
+    off-diagonal entry with |a_ij| >= theta max_k |a_ik| (d_value None or theta 0: every one); d_status (four int32) <-
+    {aggregates, rounds, largest aggregate, singletons} (include/spmv_hip_agg.h).  Arguments as for mcgs_colour.  SYNCHRONISES."""
+    check(load().spmv_hip_agg_aggregate(rows, _addr(d_row_ptr), _addr(d_column_index), _addr(d_value), theta, seed, _addr(d_agg), _addr(d_status),
+                                        _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+
+
+def agg_plan(rows, d_agg, d_status, d_member_ptr, d_member, d_work, work_bytes=None, stream=0):
+    """d_member_ptr (aggregates + 1 int32), d_member (rows int32) <- the rows aggregate by aggregate, ascending inside one; returns
+    the AggPlan that points to them and to d_agg (keep the arrays alive).  SYNCHRONISES the stream."""
+    plan = AggPlan()
+    check(load().spmv_hip_agg_plan(rows, _addr(d_agg), _addr(d_status), _addr(d_member_ptr), _addr(d_member), C.byref(plan), _addr(d_work),
+                                   _work_bytes(d_work, work_bytes), stream))
+    return plan
+
+
+def agg_galerkin_symbolic(plan, nnz, d_row_ptr, d_column_index, d_coarse_row_ptr, d_coarse_column_index, d_entry_order, d_entry_ptr, d_status,
+                          d_work, work_bytes=None, stream=0):
+    """The pattern of A_c = P' A P (d_coarse_row_ptr: aggregates + 1, d_coarse_column_index: up to nnz) and every coarse entry's run
+    of fine entries (d_entry_order: nnz, d_entry_ptr: up to nnz + 1); d_status[0] <- nnz_c.  SYNCHRONISES the stream."""
+    check(load().spmv_hip_agg_galerkin_symbolic(_plan_ref(plan), nnz, _addr(d_row_ptr), _addr(d_column_index), _addr(d_coarse_row_ptr),
+                                                _addr(d_coarse_column_index), _addr(d_entry_order), _addr(d_entry_ptr), _addr(d_status),
+                                                _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+
+
+def agg_galerkin_numeric(nnz, nnz_c, d_entry_order, d_entry_ptr, d_value, d_coarse_value, stream=0):
+    """d_coarse_value[e] <- the fine values of coarse entry e's run, added left to right from +0.0.  Only enqueues."""
+    check(load().spmv_hip_agg_galerkin_numeric(nnz, nnz_c, _addr(d_entry_order), _addr(d_entry_ptr), _addr(d_value), _addr(d_coarse_value), stream))
+
+
+def agg_restrict(plan, d_r, d_rc, stream=0, dtype=None):
+    """r_c[I] <- the sum of r over the members of aggregate I in plan order.  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_agg_restrict_" + _krylov_suffix((d_r, d_rc), dtype))
+    check(fn(_plan_ref(plan), _addr(d_r), _addr(d_rc), stream))
+
+
+def agg_prolong_add(plan, omega, d_ec, d_x, stream=0, dtype=None):
+    """x_i <- x_i + omega e_c[agg[i]] in place.  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_agg_prolong_add_" + _krylov_suffix((d_ec, d_x), dtype))
+    check(fn(_plan_ref(plan), omega, _addr(d_ec), _addr(d_x), stream))
