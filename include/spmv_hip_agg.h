@@ -69,7 +69,9 @@
  * arrays whose length a call does not know -- the columns and values of aggregate -- the first element); SPMV_HIP_ERR_ALIGN
  * for a vector or a workspace off 16-byte alignment, values off 8-byte and an index array off 4-byte alignment.
  *
- * Callers detect the feature by the presence of the symbols (SPMV_HIP_VERSION is unchanged).
+ * Callers detect the feature by the presence of the symbols (SPMV_HIP_VERSION is unchanged).  The aggregates of a distance-2
+ * independent set and a restriction by a group of lanes per aggregate, on the same d_agg, d_status and plan, are two further calls
+ * in a header of their own: spmv_hip_agg_mis2.h.
  */
 #ifndef SPMV_HIP_AGG_H
 #define SPMV_HIP_AGG_H

@@ -1,8 +1,9 @@
-// agg.hip -- include/spmv_hip_agg.h: one level of a plain aggregation multigrid over caller-owned device arrays.  The kernels are
+// agg.hip -- include/spmv_hip_agg.h and include/spmv_hip_agg_mis2.h (the aggregates of a distance-2 independent set, the restriction by
+// a group of lanes per aggregate): one level of a plain aggregation multigrid over caller-owned device arrays.  The kernels are
 // agg_kernels.hpp; the check of a call's arrays is the conjugate-gradient step's (krylov_check.hpp); the stable sorts are
 // hipCUB's radix sort and the prefix sums spmv_hip_internal_exclusive_scan_i32 (coo_sort.hip), whose temporary memory is
 // allocated and freed inside the three calls that synchronise anyway.
-#include "spmv_hip_agg.h"
+#include "spmv_hip_agg_mis2.h"
 
 #include "krylov_check.hpp"
 #include "agg_kernels.hpp"
@@ -344,6 +345,159 @@ int agg_restrict(const Plan * plan, const T * d_r, T * d_rc, void * stream)
     return SPMV_HIP_OK;
 }
 
+// ---- include/spmv_hip_agg_mis2.h ---------------------------------------------------------------------------------------------------
+
+// The workspace of the distance-2 aggregation: [counters 16: decided, missing][marks: rows bytes][beside: rows bytes][four arrays
+// of rows + 1 ints: the state, the nearest keys / the flags / the roots joined in pass 1, the ranks, the counts][thresholds: rows
+// doubles]
+struct Work2 {
+    size_t counter, marks, beside, ints[4], thresh, bytes;
+};
+Work2 work2_of(long long rows)
+{
+    Work2 w;
+    w.counter = 0;
+    w.marks = 16;
+    w.beside = w.marks + up16((size_t) rows);
+    size_t at = w.beside + up16((size_t) rows);
+    for (int k = 0; k < 4; ++k) {
+        w.ints[k] = at;
+        at += up16(((size_t) rows + 1) * 4);
+    }
+    w.thresh = at;
+    at += up16((size_t) rows * 8);
+    w.bytes = at;
+    return w;
+}
+
+int agg_aggregate_mis2(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta, uint32_t seed,
+                       int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
+{
+    if (rows < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "rows < 0");
+    if (!d_row_ptr || !d_column_index || !d_agg || !d_status || !d_work)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_value may be null)");
+    if (!std::isfinite(theta) || !(theta >= 0.0) || !(theta <= 1.0))
+        return fail(SPMV_HIP_ERR_INVALID, "theta is not inside [0, 1]");
+    const Work2 w = work2_of(rows);
+    const KrylovArray arrays[] = {{d_row_ptr, ((unsigned long long) rows + 1) * 4, false, 4, "d_row_ptr"},
+                                  {d_column_index, 4, false, 4, "d_column_index"},
+                                  {d_value, 8, false, 8, "d_value"},
+                                  {d_agg, (unsigned long long) rows * 4, true, 4, "d_agg"},
+                                  {d_status, 16, true, 4, "d_status"},
+                                  {d_work, w.bytes, true, 16, "d_work"}};
+    int rc = krylov_check_arrays(rows, 4, arrays, (int) (sizeof arrays / sizeof arrays[0]));
+    if (rc != 0)
+        return rc;
+    rc = krylov_check_work(work_bytes, w.bytes, "rows", "spmv_hip_agg_mis2_workspace(rows)");
+    if (rc != 0)
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (rows == 0) {
+        HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return SPMV_HIP_OK;
+    }
+    char * work = static_cast<char *>(d_work);
+    int * decided = reinterpret_cast<int *>(work + w.counter);
+    int * missing = decided + 1;
+    unsigned char * mark = reinterpret_cast<unsigned char *>(work + w.marks);
+    unsigned char * beside = reinterpret_cast<unsigned char *>(work + w.beside);
+    int * state = reinterpret_cast<int *>(work + w.ints[0]);
+    int * near = reinterpret_cast<int *>(work + w.ints[1]); // in the rounds; then the flags of the roots; then the roots joined in pass 1
+    int * flag = near, * joined = near;
+    int * rank = reinterpret_cast<int *>(work + w.ints[2]);
+    int * count = reinterpret_cast<int *>(work + w.ints[3]);
+    const double * thresh = d_value && theta > 0.0 ? reinterpret_cast<double *>(work + w.thresh) : nullptr;
+    const unsigned grid = blocks_of(rows > 4 ? rows : 4);
+    const dim3 g(grid), b(256);
+    hipLaunchKernelGGL(spmv::agg_init_kernel, g, b, 0, s, (int) rows, d_row_ptr, d_column_index, d_value, theta, state, const_cast<double *>(thresh),
+                       d_status);
+    HIP_TRY(hipGetLastError());
+    long long left = rows;
+    int rounds = 0;
+    while (left > 0) {
+        HIP_TRY(hipMemsetAsync(decided, 0, 4, s));
+        hipLaunchKernelGGL(spmv::agg_mis2_near_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, near);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(spmv::agg_mis2_mark_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, near,
+                           mark);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(spmv::agg_mis2_beside_kernel, g, b, 0, s, (int) rows, d_row_ptr, d_column_index, d_value, thresh, mark, beside);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(spmv::agg_mis2_assign_kernel, g, b, 0, s, (int) rows, d_row_ptr, d_column_index, d_value, thresh, state, mark, beside,
+                           decided);
+        HIP_TRY(hipGetLastError());
+        int got = 0;
+        HIP_TRY(hipMemcpyAsync(&got, decided, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (got <= 0 || got > left) // the largest remaining key always wins: arrays that changed under the call, or not a CSR matrix
+            return fail(SPMV_HIP_ERR_STATE, "an aggregation round that decided no row: the arrays are not those of a CSR matrix");
+        left -= got;
+        ++rounds;
+    }
+    hipLaunchKernelGGL(spmv::agg_flag_kernel, dim3(blocks_of((long long) rows + 1)), b, 0, s, (int) rows, state, flag);
+    HIP_TRY(hipGetLastError());
+    if (spmv_hip_internal_exclusive_scan_i32(flag, rank, (long long) rows + 1, s) != 0)
+        return fail(SPMV_HIP_ERR_HIP, "the prefix sum over the roots");
+    HIP_TRY(hipMemsetAsync(count, 0, (size_t) rows * 4, s));
+    HIP_TRY(hipMemsetAsync(missing, 0, 4, s));
+    hipLaunchKernelGGL(spmv::agg_mis2_join1_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, joined);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(spmv::agg_mis2_join2_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, joined,
+                       rank, d_agg, count, missing);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(spmv::agg_status_kernel, g, b, 0, s, (int) rows, rounds, rank, count, d_status);
+    HIP_TRY(hipGetLastError());
+    int none = 0;
+    HIP_TRY(hipMemcpyAsync(&none, missing, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (none != 0)
+        return fail(SPMV_HIP_ERR_STATE, "a covered row without a neighbour that joined a root: the arrays changed under the call");
+    return SPMV_HIP_OK;
+}
+
+bool group_ok(int32_t group) { return group >= 1 && group <= spmv::kWave && (group & (group - 1)) == 0; }
+
+template <class T, int G>
+void launch_group(const Plan * plan, const T * d_r, T * d_rc, hipStream_t s)
+{
+    const long long per_wave = (long long) spmv::kAggGroupPasses * (spmv::kWave / G);
+    const long long waves = (plan->aggregates + per_wave - 1) / per_wave;
+    hipLaunchKernelGGL((spmv::agg_restrict_group_kernel<T, G>), dim3(krylov_blocks(waves)), dim3(256), 0, s, plan->aggregates, plan->d_member_ptr,
+                       plan->d_member, d_r, d_rc);
+}
+
+template <class T>
+int agg_restrict_group(const Plan * plan, int32_t group, const T * d_r, T * d_rc, void * stream)
+{
+    int rc = check_plan(plan);
+    if (rc != 0)
+        return rc;
+    if (!group_ok(group))
+        return fail(SPMV_HIP_ERR_INVALID, "group is not a power of two in 1 ... 64");
+    if (group == 1)
+        return agg_restrict(plan, d_r, d_rc, stream); // the same sums by contract: the same kernel
+    if (!d_r || !d_rc)
+        return fail(SPMV_HIP_ERR_INVALID, "null device pointer");
+    rc = check_vectors<T>(plan, d_r, false, d_rc, "d_r", "d_rc");
+    if (rc != 0)
+        return rc;
+    if (plan->rows == 0)
+        return SPMV_HIP_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (group) {
+    case 2: launch_group<T, 2>(plan, d_r, d_rc, s); break;
+    case 4: launch_group<T, 4>(plan, d_r, d_rc, s); break;
+    case 8: launch_group<T, 8>(plan, d_r, d_rc, s); break;
+    case 16: launch_group<T, 16>(plan, d_r, d_rc, s); break;
+    case 32: launch_group<T, 32>(plan, d_r, d_rc, s); break;
+    default: launch_group<T, 64>(plan, d_r, d_rc, s); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return SPMV_HIP_OK;
+}
+
 template <class T>
 int agg_prolong_add(const Plan * plan, double omega, const T * d_ec, T * d_x, void * stream)
 {
@@ -417,6 +571,40 @@ int spmv_hip_agg_prolong_add_f64(const struct spmv_hip_agg_plan * plan, double o
 int spmv_hip_agg_prolong_add_f32(const struct spmv_hip_agg_plan * plan, double omega, const float * d_ec, float * d_x, void * stream)
 {
     return agg_prolong_add(plan, omega, d_ec, d_x, stream);
+}
+
+int spmv_hip_agg_mis2_workspace(int32_t rows, size_t * bytes)
+{
+    if (rows < 0 || !bytes)
+        return fail(SPMV_HIP_ERR_INVALID, "rows < 0, or bytes is null");
+    *bytes = work2_of(rows).bytes;
+    return SPMV_HIP_OK;
+}
+
+int spmv_hip_agg_aggregate_mis2(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta,
+                                uint32_t seed, int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
+{
+    return agg_aggregate_mis2(rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes, stream);
+}
+
+int spmv_hip_agg_restrict_group_f64(const struct spmv_hip_agg_plan * plan, int32_t group, const double * d_r, double * d_rc, void * stream)
+{
+    return agg_restrict_group(plan, group, d_r, d_rc, stream);
+}
+
+int spmv_hip_agg_restrict_group_f32(const struct spmv_hip_agg_plan * plan, int32_t group, const float * d_r, float * d_rc, void * stream)
+{
+    return agg_restrict_group(plan, group, d_r, d_rc, stream);
+}
+
+int32_t spmv_hip_agg_group(const struct spmv_hip_agg_plan * plan)
+{
+    if (!plan || plan->rows <= 0 || plan->aggregates <= 0)
+        return 1;
+    int32_t g = 1;
+    while (g < spmv::kWave && (long long) g * plan->aggregates < plan->rows)
+        g *= 2;
+    return g;
 }
 
 } // extern "C"

@@ -14,6 +14,11 @@
 //
 // The aggregation, the member lists and the Galerkin product are one-time code: a lane per row or per entry, integer atomics for
 // the counters only.
+//
+// include/spmv_hip_agg_mis2.h adds, at the end of this file, agg_restrict_group_kernel<T, G> -- G = 2 ... 64 lanes per aggregate
+// that stride its member list and meet in group_sum<G> -- and the six one-time kernels of the aggregation by a distance-2
+// independent set: four per round (the nearest undecided key, the marks, who is beside a mark, the states) and the two passes in
+// which rows join roots.
 #pragma once
 
 #include "cg_updates.hpp"
@@ -416,6 +421,273 @@ __global__ __launch_bounds__(256, 8) void agg_restrict_kernel(int aggregates, in
             if (I[u] < aggregates)
                 rc[I[u]] = (T) s[u];
     }
+}
+
+// ---- the restriction by a group of lanes per aggregate (include/spmv_hip_agg_mis2.h) -----------------------------------------------
+
+// G lanes per aggregate, 64 / G aggregates per pass of the wave, kAggGroupPasses passes per wave, all four in flight.  Every
+// lane of a group loads its aggregate's member_ptr pair in one 8-byte load (one address per group: one fetch); lane l takes the
+// members l, l + G, ... -- a lane's own members lie G apart, which is why its loads are 4 bytes wide, and the G lanes of a group
+// read G consecutive words -- two of them with their gathers of r in flight per aggregate, added in that order (the contract) with
+// a test per member; members beyond the first 2 G run in a rolled loop of such pairs.  The loops end per lane; behind them every
+// lane of the wave is active again, a lane without a member (or without an aggregate) holding +0.0, and the group's sums meet in
+// group_sum<G>: p += p[lane ^ step], step = 1 ... G / 2.  The group's first lane stores.
+constexpr int kAggGroupPasses = 4;
+
+template <class T, int G>
+__global__ __launch_bounds__(256, 8) void agg_restrict_group_kernel(int aggregates, const int * __restrict__ member_ptr,
+                                                                    const int * __restrict__ member, const T * __restrict__ r, T * __restrict__ rc)
+{
+    static_assert(G >= 2, "a group of one lane is agg_restrict_kernel");
+    constexpr int PER = kWave / G; // aggregates of one pass of the wave
+    constexpr int U = 4;           // passes in flight
+    constexpr int V = 2;           // members of a lane in flight per aggregate
+    static_assert(kAggGroupPasses % U == 0, "whole passes");
+    const int wave = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
+    const long long base = ((long long) blockIdx.x * 4 + wave) * (kAggGroupPasses * PER);
+    if (base >= aggregates)
+        return; // the whole wave
+    const int lane = (int) threadIdx.x & (kWave - 1);
+    const int l = lane & (G - 1), g = lane / G;
+#pragma unroll 1
+    for (int j = 0; j < kAggGroupPasses; j += U) {
+        long long I[U];
+        int k[U], end[U], m[U][V];
+        double v[U][V], s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            I[u] = base + (long long) (j + u) * PER + g;
+            k[u] = end[u] = 0;
+            if (I[u] < aggregates) {
+                const agg_i2 p = *reinterpret_cast<const agg_i2 *>(member_ptr + I[u]);
+                k[u] = p[0] + l;
+                end[u] = p[1];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < V; ++t) {
+                m[u][t] = 0;
+                if (k[u] + t * G < end[u])
+                    m[u][t] = member[k[u] + t * G];
+            }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < V; ++t) {
+                v[u][t] = 0.0;
+                if (k[u] + t * G < end[u])
+                    v[u][t] = (double) r[m[u][t]];
+            }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            s[u] = 0.0;
+#pragma unroll
+            for (int t = 0; t < V; ++t)
+                if (k[u] + t * G < end[u])
+                    s[u] += v[u][t];
+        }
+        // aggregates of more than 2 G rows
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            for (int q = k[u] + V * G; q < end[u]; q += V * G) {
+                int mq[V];
+                double w[V];
+#pragma unroll
+                for (int t = 0; t < V; ++t) {
+                    mq[t] = 0;
+                    if (q + t * G < end[u])
+                        mq[t] = member[q + t * G];
+                }
+#pragma unroll
+                for (int t = 0; t < V; ++t) {
+                    w[t] = 0.0;
+                    if (q + t * G < end[u])
+                        w[t] = (double) r[mq[t]];
+                }
+#pragma unroll
+                for (int t = 0; t < V; ++t)
+                    if (q + t * G < end[u])
+                        s[u] += w[t];
+            }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            s[u] = group_sum<G>(s[u]); // every lane of the wave is active again
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (l == 0 && I[u] < aggregates)
+                rc[I[u]] = (T) s[u];
+    }
+}
+
+// ---- the aggregation by a distance-2 independent set (include/spmv_hip_agg_mis2.h) -------------------------------------------------
+
+// whether the key of row a (its hash ha) is above the key of row b
+__device__ __forceinline__ bool agg_key_above(unsigned ha, int a, unsigned hb, int b)
+{
+    return ha > hb || (ha == hb && a > b);
+}
+
+// near[i] <- the undecided row of {i} + N(i) with the largest key, -1 without one: every row relays, whatever its state
+__global__ __launch_bounds__(256) void agg_mis2_near_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr,
+                                                            const int * __restrict__ column_index, const double * __restrict__ value,
+                                                            const double * __restrict__ thresh, const int * __restrict__ state,
+                                                            int * __restrict__ near)
+{
+    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
+    if (i >= rows)
+        return;
+    int best = state[i] == kAggUndecided ? (int) i : -1;
+    unsigned hb = agg_fmix32((unsigned) i ^ seed);
+    const int end = row_ptr[i + 1];
+    for (int e = row_ptr[i]; e < end; ++e) {
+        const int j = column_index[e];
+        if (j == (int) i || state[j] != kAggUndecided || !agg_strong(value, thresh, e, i))
+            continue;
+        const unsigned hj = agg_fmix32((unsigned) j ^ seed);
+        if (best < 0 || agg_key_above(hj, j, hb, best)) {
+            best = j;
+            hb = hj;
+        }
+    }
+    near[i] = best;
+}
+
+// mark[i] <- 1 where row i is undecided and no near[j], j in {i} + N(i), has a key above its own: the largest within two steps
+__global__ __launch_bounds__(256) void agg_mis2_mark_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr,
+                                                            const int * __restrict__ column_index, const double * __restrict__ value,
+                                                            const double * __restrict__ thresh, const int * __restrict__ state,
+                                                            const int * __restrict__ near, unsigned char * __restrict__ mark)
+{
+    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
+    if (i >= rows)
+        return;
+    bool win = state[i] == kAggUndecided && near[i] == (int) i;
+    if (win) {
+        const unsigned hi = agg_fmix32((unsigned) i ^ seed);
+        const int end = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end && win; ++e) {
+            const int j = column_index[e];
+            if (j == (int) i || !agg_strong(value, thresh, e, i))
+                continue;
+            const int n = near[j];
+            if (n >= 0 && agg_key_above(agg_fmix32((unsigned) n ^ seed), n, hi, (int) i))
+                win = false;
+        }
+    }
+    mark[i] = win ? 1 : 0;
+}
+
+// beside[i] <- 1 where row i or one of its neighbours is marked
+__global__ __launch_bounds__(256) void agg_mis2_beside_kernel(int rows, const int * __restrict__ row_ptr, const int * __restrict__ column_index,
+                                                              const double * __restrict__ value, const double * __restrict__ thresh,
+                                                              const unsigned char * __restrict__ mark, unsigned char * __restrict__ beside)
+{
+    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
+    if (i >= rows)
+        return;
+    bool yes = mark[i] != 0;
+    const int end = row_ptr[i + 1];
+    for (int e = row_ptr[i]; e < end && !yes; ++e) {
+        const int j = column_index[e];
+        yes = j != (int) i && agg_strong(value, thresh, e, i) && mark[j] != 0;
+    }
+    beside[i] = yes ? 1 : 0;
+}
+
+// A marked row becomes a root; an undecided row that is not marked and has beside[j] for a j of {i} + N(i) becomes covered.  A
+// lane reads the state of its own row alone, and the marks and `beside` of the others.  *decided += the rows that left the undecided.
+__global__ __launch_bounds__(256) void agg_mis2_assign_kernel(int rows, const int * __restrict__ row_ptr, const int * __restrict__ column_index,
+                                                              const double * __restrict__ value, const double * __restrict__ thresh, int * state,
+                                                              const unsigned char * __restrict__ mark, const unsigned char * __restrict__ beside,
+                                                              int * __restrict__ decided)
+{
+    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
+    int to = 0;
+    if (i < rows && state[i] == kAggUndecided) {
+        if (mark[i]) {
+            to = kAggRoot;
+        } else if (beside[i]) {
+            to = kAggCovered;
+        } else {
+            const int end = row_ptr[i + 1];
+            for (int e = row_ptr[i]; e < end && to == 0; ++e) {
+                const int j = column_index[e];
+                if (j != (int) i && agg_strong(value, thresh, e, i) && beside[j])
+                    to = kAggCovered;
+            }
+        }
+        if (to != 0)
+            state[i] = to;
+    }
+    agg_wave_count(to != 0, decided);
+}
+
+// pass 1: joined[i] <- i for a root, the root among the neighbours with the largest key for a row beside one, else -1
+__global__ __launch_bounds__(256) void agg_mis2_join1_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr,
+                                                             const int * __restrict__ column_index, const double * __restrict__ value,
+                                                             const double * __restrict__ thresh, const int * __restrict__ state,
+                                                             int * __restrict__ joined)
+{
+    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
+    if (i >= rows)
+        return;
+    int root = (int) i;
+    if (state[i] != kAggRoot) {
+        root = -1;
+        unsigned hr = 0;
+        const int end = row_ptr[i + 1];
+        for (int e = row_ptr[i]; e < end; ++e) {
+            const int j = column_index[e];
+            if (j == (int) i || state[j] != kAggRoot || !agg_strong(value, thresh, e, i))
+                continue;
+            const unsigned hj = agg_fmix32((unsigned) j ^ seed);
+            if (root < 0 || agg_key_above(hj, j, hr, root)) {
+                root = j;
+                hr = hj;
+            }
+        }
+    }
+    joined[i] = root;
+}
+
+// pass 2: a row that joined nobody in pass 1 joins the root that one of its neighbours joined in pass 1 (a neighbour that is no
+// root itself), the largest key among those roots; agg[i] <- the number of the row's root, count[agg[i]] += 1; *missing += the
+// rows that found none (they are counted in aggregate 0).  `joined` is read only: what pass 2 finds is stored in agg alone.
+__global__ __launch_bounds__(256) void agg_mis2_join2_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr,
+                                                             const int * __restrict__ column_index, const double * __restrict__ value,
+                                                             const double * __restrict__ thresh, const int * __restrict__ state,
+                                                             const int * __restrict__ joined, const int * __restrict__ rank,
+                                                             int * __restrict__ agg, int * __restrict__ count, int * __restrict__ missing)
+{
+    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
+    bool none = false;
+    if (i < rows) {
+        int root = joined[i];
+        if (root < 0) {
+            unsigned hr = 0;
+            const int end = row_ptr[i + 1];
+            for (int e = row_ptr[i]; e < end; ++e) {
+                const int j = column_index[e];
+                if (j == (int) i || state[j] == kAggRoot || !agg_strong(value, thresh, e, i))
+                    continue;
+                const int q = joined[j];
+                if (q < 0 || q >= rows)
+                    continue;
+                const unsigned hq = agg_fmix32((unsigned) q ^ seed);
+                if (root < 0 || agg_key_above(hq, q, hr, root)) {
+                    root = q;
+                    hr = hq;
+                }
+            }
+        }
+        none = root < 0;
+        const int a = none ? 0 : rank[root];
+        agg[i] = a;
+        atomicAdd(count + a, 1);
+    }
+    agg_wave_count(none, missing);
 }
 
 } // namespace spmv

@@ -1,7 +1,7 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
 spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h,
-spmv_hip_cheby.h, spmv_hip_mcgs.h and spmv_hip_agg.h (the C ABI of libspmv_hip.so).
+spmv_hip_cheby.h, spmv_hip_mcgs.h, spmv_hip_agg.h and spmv_hip_agg_mis2.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -28,7 +28,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
                                           "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h",
-                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h", "spmv_hip_agg.h")]
+                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h", "spmv_hip_agg.h", "spmv_hip_agg_mis2.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -227,6 +227,12 @@ SIGNATURES = {
     "spmv_hip_agg_restrict_f32": (C.c_int, [_vp] * 4),
     "spmv_hip_agg_prolong_add_f64": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp]),
     "spmv_hip_agg_prolong_add_f32": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp]),
+    # spmv_hip_agg_mis2.h
+    "spmv_hip_agg_mis2_workspace": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "spmv_hip_agg_aggregate_mis2": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_double, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "spmv_hip_agg_restrict_group_f64": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
+    "spmv_hip_agg_restrict_group_f32": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
+    "spmv_hip_agg_group": (C.c_int32, [_vp]),
 }
 
 
@@ -1415,3 +1421,29 @@ def agg_prolong_add(plan, omega, d_ec, d_x, stream=0, dtype=None):
     """x_i <- x_i + omega e_c[agg[i]] in place.  Arguments as for cg_step.  Only enqueues."""
     fn = getattr(load(), "spmv_hip_agg_prolong_add_" + _krylov_suffix((d_ec, d_x), dtype))
     check(fn(_plan_ref(plan), omega, _addr(d_ec), _addr(d_x), stream))
+
+
+def agg_mis2_workspace_bytes(rows):
+    """The workspace of agg_aggregate_mis2: a function of rows alone (include/spmv_hip_agg_mis2.h)."""
+    b = C.c_size_t(0)
+    check(load().spmv_hip_agg_mis2_workspace(rows, C.byref(b)))
+    return b.value
+
+
+def agg_aggregate_mis2(rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes=None, stream=0):
+    """d_agg, d_status <- the aggregates of a distance-2 independent set of roots: arguments, neighbours, keys and status as for
+    agg_aggregate, the workspace agg_mis2_workspace_bytes(rows) (include/spmv_hip_agg_mis2.h).  SYNCHRONISES."""
+    check(load().spmv_hip_agg_aggregate_mis2(rows, _addr(d_row_ptr), _addr(d_column_index), _addr(d_value), theta, seed, _addr(d_agg),
+                                             _addr(d_status), _addr(d_work), _work_bytes(d_work, work_bytes), stream))
+
+
+def agg_restrict_group(plan, group, d_r, d_rc, stream=0, dtype=None):
+    """r_c[I] <- the sum of r over the members of aggregate I by `group` lanes (a power of two in 1 ... 64) and their butterfly;
+    group 1 is agg_restrict.  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_agg_restrict_group_" + _krylov_suffix((d_r, d_rc), dtype))
+    check(fn(_plan_ref(plan), group, _addr(d_r), _addr(d_rc), stream))
+
+
+def agg_group(plan):
+    """The recommended group of agg_restrict_group: the smallest power of two >= rows / aggregates inside 1 ... 64; host arithmetic."""
+    return int(load().spmv_hip_agg_group(_plan_ref(plan)))

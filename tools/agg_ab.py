@@ -19,11 +19,18 @@
              Chebyshev polynomial of --coarse-degree stands for the solve (a fixed symmetric operator: CG stays valid).  Iterations and
              seconds, the set-up of the hierarchy, its plans and its smoothers reported beside them.  Reported only.
 
+--mis2 (include/spmv_hip_agg_mis2.h): the hierarchy by spmv_hip_agg_aggregate_mis2; in `transfer` spmv_hip_agg_restrict_group at
+spmv_hip_agg_group(plan) lanes beside spmv_hip_agg_restrict on the same plan, each against the triad by counted bytes with the
+target of the counted bytes at the triad's rate x 1.16 ("met" / "missed"); in `pcg` the V-cycle down to <= --floor rows with its
+dense coarsest solve and the grouped restriction on every level, at omega 1, 1.5 and 2, and then the distance-1 cycle above built
+and run in the same process.  The log goes to profiles/agg_mis2_ab.log.
+
 Three warm-up rounds, then --rounds rounds alternating the ways, medians.  The log goes to stdout and to profiles/agg_ab.log
 (--log).
 
     python tools/agg_ab.py
     python tools/agg_ab.py --only poisson_4096 --rounds 25 --no-pcg
+    python tools/agg_ab.py --mis2
 """
 import argparse
 import json
@@ -53,23 +60,27 @@ class Level:
     pass
 
 
-def hierarchy(torch, capi, rows, tp, tc, tv, floor, s):
-    """The levels from the device CSR arrays down to <= floor rows: every level's matrix and, but for the last, its plan."""
+def hierarchy(torch, capi, rows, tp, tc, tv, floor, s, mis2=False):
+    """The levels from the device CSR arrays down to <= floor rows: every level's matrix and, but for the last, its plan.  mis2: the
+    aggregates of spmv_hip_agg_aggregate_mis2, and spmv_hip_agg_group(plan) lanes per aggregate in the level's restriction."""
     dev = tp.device
     i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
     levels, n = [], rows
     while True:
         L = Level()
-        L.n, L.nnz, L.tp, L.tc, L.tv, L.plan = n, int(tp[-1]), tp, tc, tv, None
+        L.n, L.nnz, L.tp, L.tc, L.tv, L.plan, L.group = n, int(tp[-1]), tp, tc, tv, None, 1
         levels.append(L)
         if n <= floor or len(levels) >= MAX_LEVELS:
             break
         nnz = L.nnz
-        work = torch.zeros(capi.agg_workspace_bytes(n, nnz) // 8, **f64)
+        work = torch.zeros(max(capi.agg_workspace_bytes(n, nnz), capi.agg_mis2_workspace_bytes(n) if mis2 else 0) // 8, **f64)
         L.agg, status = torch.zeros(n, **i32), torch.zeros(4, **i32)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        capi.agg_aggregate(n, tp, tc, tv, 0.0, 0, L.agg, status, work, capi.agg_workspace_bytes(n), s)
+        if mis2:
+            capi.agg_aggregate_mis2(n, tp, tc, tv, 0.0, 0, L.agg, status, work, capi.agg_mis2_workspace_bytes(n), s)
+        else:
+            capi.agg_aggregate(n, tp, tc, tv, 0.0, 0, L.agg, status, work, capi.agg_workspace_bytes(n), s)
         t1 = time.perf_counter()
         st = status.cpu().numpy().tolist()
         aggregates = st[0]
@@ -78,6 +89,7 @@ def hierarchy(torch, capi, rows, tp, tc, tv, floor, s):
         t2 = time.perf_counter()
         L.plan = capi.agg_plan(n, L.agg, status, L.mptr, L.member, work, capi.agg_workspace_bytes(n), s)
         t3 = time.perf_counter()
+        L.group = capi.agg_group(L.plan) if mis2 else 1
         cp, cc, order, eptr = torch.zeros(aggregates + 1, **i32), torch.zeros(max(1, nnz), **i32), torch.zeros(max(1, nnz), **i32), torch.zeros(nnz + 1, **i32)
         cstatus = torch.zeros(1, **i32)
         torch.cuda.synchronize()
@@ -126,6 +138,9 @@ def transfer(torch, capi, L, rounds, s):
                 "prolong_add": lambda: capi.agg_prolong_add(L.plan, 1e-3, e, x, s),
                 "torch_add_gather": lambda: x.add_(e[index], alpha=1e-3),
                 "triad": (lambda: capi.triad(n, a.data_ptr(), b.data_ptr(), c.data_ptr(), 3.1, s)) if size == 8 else (lambda: torch.add(b, c, alpha=3.1, out=a))}
+        rcg = torch.zeros(na, dtype=dtype, device=dev)
+        if L.group > 1:
+            ways["restrict_group"] = lambda: capi.agg_restrict_group(L.plan, L.group, r, rcg, s)
         med = alternate(torch, ways, rounds)
         close = float((kept["rc"].double() - rc.double()).abs().max()) if na else 0.0
         bytes_ = {"restrict": n * (4 + size) + na * (4 + size), "prolong_add": n * (4 + 2 * size) + na * size, "triad": 3 * n * size}
@@ -140,6 +155,14 @@ def transfer(torch, capi, L, rounds, s):
                      "triad_GBps": round(bytes_["triad"] / med["triad"] / 1e3, 1),
                      "triad_is": "capi.triad" if size == 8 else "torch.add(b, c, alpha=s, out=a)",
                      "index_dtype": str(index.dtype), "restrict_against_index_add_max_abs": close}
+        if L.group > 1:
+            # the target of DESIGN 3.23: the time of the counted bytes at the triad's rate, times 1.16
+            ratio = med["restrict_group"] / bytes_["restrict"] / per_byte
+            out[name].update({"group": L.group, "restrict_group_over_restrict": round(med["restrict_group"] / med["restrict"], 3),
+                              "restrict_group_over_triad_by_bytes": round(ratio, 3), "restrict_group_GBps": round(bytes_["restrict"] / med["restrict_group"] / 1e3, 1),
+                              "restrict_group_target_1.16": "met" if ratio <= 1.16 else "missed",
+                              "restrict_target_1.16": "met" if med["restrict"] / bytes_["restrict"] / per_byte <= 1.16 else "missed",
+                              "restrict_group_against_restrict_max_abs": float((rcg.double() - rc.double()).abs().max()) if na else 0.0})
     return out
 
 
@@ -193,7 +216,10 @@ def v_cycle(torch, capi, levels, omega, coarse_degree, s):
         below = levels[k + 1]
         polynomial(L, 2, L.table, r, z)
         L.c16.spmv_f64_scaled(L.P, L.C, L.A, z.data_ptr(), -1.0, 1.0, r.data_ptr(), L.t.data_ptr(), s)
-        capi.agg_restrict(L.plan, L.t, below.r, s)
+        if L.group > 1:
+            capi.agg_restrict_group(L.plan, L.group, L.t, below.r, s)
+        else:
+            capi.agg_restrict(L.plan, L.t, below.r, s)
         cycle(k + 1, below.r, below.z)
         capi.agg_prolong_add(L.plan, omega, below.z, z, s)
         L.c16.spmv_f64_scaled(L.P, L.C, L.A, z.data_ptr(), -1.0, 1.0, r.data_ptr(), L.t.data_ptr(), s)
@@ -203,7 +229,7 @@ def v_cycle(torch, capi, levels, omega, coarse_degree, s):
     return lambda src, z: cycle(0, src, z)
 
 
-def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s):
+def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s, omegas=(1.0, 1.5), baselines=True):
     top = levels[0]
     n, dev = top.n, rhs.device
     f64 = dict(dtype=torch.float64, device=dev)
@@ -238,7 +264,8 @@ def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s):
         return apply
 
     out = {}
-    for way, apply in (("diagonal", diagonal), ("chebyshev_3", chebyshev), ("v_cycle_omega_1.0", cycle_at(1.0)), ("v_cycle_omega_1.5", cycle_at(1.5))):
+    ways = ([("diagonal", diagonal), ("chebyshev_3", chebyshev)] if baselines else []) + [("v_cycle_omega_%.1f" % w, cycle_at(w)) for w in omegas]
+    for way, apply in ways:
         x.zero_()
         r.copy_(rhs)
         torch.cuda.synchronize()
@@ -265,7 +292,30 @@ def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s):
     return out
 
 
-def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degree, solve):
+def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, omegas=(1.0, 1.5), baselines=True):
+    """PCG with the V-cycle over `levels` into res: the cycle's levels, its set-up and res["pcg"]."""
+    # the cycle's levels: down to the floor, or to the first level that the aggregation shrinks by less than --stall
+    depth = 0
+    while depth + 1 < len(levels) and levels[depth].n > floor and levels[depth].n >= stall * levels[depth + 1].n:
+        depth += 1
+    used = levels[:depth + 1]
+    if depth == 0:
+        return
+    t0 = time.perf_counter()
+    prepare_cycle(torch, capi, used, dense_limit, coarse_degree, s)
+    res["cycle_setup_seconds"] = round(time.perf_counter() - t0, 4)
+    res["cycle_levels"] = [L.n for L in used]
+    res["coarsest"] = "dense inverse" if used[-1].inverse is not None else "Chebyshev polynomial of degree %d over [lambda / %g, lambda]" % (coarse_degree, RATIO)
+    gen = torch.Generator(device=levels[0].tp.device)
+    gen.manual_seed(9)
+    rhs = torch.rand(rows, generator=gen, dtype=torch.float64, device=levels[0].tp.device) * 2 - 1
+    res["pcg"] = pcg(torch, capi, used, rhs, cap, look, coarse_degree, s, omegas, baselines)
+    for L in used:
+        if L.inverse is None:
+            L.c16.close()
+
+
+def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degree, solve, mis2=False):
     import torch
     from spmv_amd import capi
     dev = torch.device("cuda:0")
@@ -273,37 +323,30 @@ def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degr
     assert rows == cols
     nnz = int(p_h[-1])
     s = torch.cuda.current_stream().cuda_stream
-    res = {"matrix": name, "spec": spec, "rows": rows, "stored_entries": nnz, "rounds": rounds, "library": os.path.basename(capi.LIB_PATH)}
+    res = {"matrix": name, "spec": spec, "rows": rows, "stored_entries": nnz, "rounds": rounds, "library": os.path.basename(capi.LIB_PATH),
+           "aggregation": "distance 2" if mis2 else "distance 1"}
     tp, tc, tv = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (p_h, c_h, v_h))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    levels = hierarchy(torch, capi, rows, tp, tc, tv, floor, s)
+    levels = hierarchy(torch, capi, rows, tp, tc, tv, floor, s, mis2)
     res["hierarchy_seconds"] = round(time.perf_counter() - t0, 4)
-    res["levels"] = [{"rows": L.n, "stored_entries": L.nnz, "status": getattr(L, "status", None), "seconds": getattr(L, "seconds", None)} for L in levels]
+    res["levels"] = [{"rows": L.n, "stored_entries": L.nnz, "status": getattr(L, "status", None), "seconds": getattr(L, "seconds", None),
+                      "group": L.group} for L in levels]
     res["operator_complexity"] = round(sum(L.nnz for L in levels) / max(1, nnz), 3)
     res["setup_seconds"] = {k: round(sum(L.seconds[k] for L in levels if L.plan is not None), 4) for k in ("aggregate", "plan", "symbolic", "numeric")}
     if levels[0].plan is not None:
         res["transfer"] = transfer(torch, capi, levels[0], rounds, s)
     if solve and len(levels) > 1:
-        # the cycle's levels: down to the floor, or to the first level that the aggregation shrinks by less than --stall
-        depth = 0
-        while depth + 1 < len(levels) and levels[depth].n > floor and levels[depth].n >= stall * levels[depth + 1].n:
-            depth += 1
-        used = levels[:depth + 1]
-        if depth == 0:
-            return res
-        t0 = time.perf_counter()
-        prepare_cycle(torch, capi, used, dense_limit, coarse_degree, s)
-        res["cycle_setup_seconds"] = round(time.perf_counter() - t0, 4)
-        res["cycle_levels"] = [L.n for L in used]
-        res["coarsest"] = "dense inverse" if used[-1].inverse is not None else "Chebyshev polynomial of degree %d over [lambda / %g, lambda]" % (coarse_degree, RATIO)
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(9)
-        rhs = torch.rand(rows, generator=gen, dtype=torch.float64, device=dev) * 2 - 1
-        res["pcg"] = pcg(torch, capi, used, rhs, cap, look, coarse_degree, s)
-        for L in used:
-            if L.inverse is None:
-                L.c16.close()
+        solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, (1.0, 1.5, 2.0) if mis2 else (1.0, 1.5))
+        if mis2:
+            # the distance-1 cycle of DESIGN 3.24 in the same process, its hierarchy and set-up timed the same way
+            del levels
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            levels = hierarchy(torch, capi, rows, tp, tc, tv, floor, s, False)
+            one = {"hierarchy_seconds": round(time.perf_counter() - t0, 4)}
+            solve_with(torch, capi, levels, one, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, (1.0, 1.5), False)
+            res["distance_1"] = one
     return res
 
 
@@ -318,29 +361,33 @@ def main():
     ap.add_argument("--coarse-degree", type=int, default=16, help="the degree of the polynomial that stands for the solve on a larger coarsest level")
     ap.add_argument("--only", nargs="*", default=None, help="matrix names")
     ap.add_argument("--no-pcg", action="store_true")
-    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "agg_ab.log"))
+    ap.add_argument("--mis2", action="store_true", help="the distance-2 aggregates and the grouped restriction of spmv_hip_agg_mis2.h; the log "
+                    "goes to profiles/agg_mis2_ab.log")
+    ap.add_argument("--log", default=None)
     args = ap.parse_args()
-    log = open(args.log, "w")
+    log = open(args.log or os.path.join(ROOT, "profiles", "agg_mis2_ab.log" if args.mis2 else "agg_ab.log"), "w")
 
     def say(text):
         print(text, flush=True)
         log.write(text + "\n")
         log.flush()
 
-    say("plain aggregation (theta 0, seed 0) down to <= %d rows; restriction and prolongation against torch and beside the triad; one process, torch "
-        "events on one stream, 3 warm-up rounds, then %d rounds alternating the ways, medians" % (args.floor, args.rounds))
+    say("plain aggregation (theta 0, seed 0%s) down to <= %d rows; restriction and prolongation against torch and beside the triad; one process, torch "
+        "events on one stream, 3 warm-up rounds, then %d rounds alternating the ways, medians" % (
+            ", distance-2 roots, spmv_hip_agg_group(plan) lanes per aggregate in the grouped restriction" if args.mis2 else "", args.floor, args.rounds))
     for name, spec, what, spd in MATRICES:
         if args.only and name not in args.only:
             continue
-        res = matrix(name, spec, args.rounds, args.cap, args.look, args.floor, args.stall, args.dense_limit, args.coarse_degree, spd and not args.no_pcg)
+        res = matrix(name, spec, args.rounds, args.cap, args.look, args.floor, args.stall, args.dense_limit, args.coarse_degree, spd and not args.no_pcg,
+                     args.mis2)
         say("%-13s %s: %d rows, %d stored entries; %s" % (name, what, res["rows"], res["stored_entries"], res["library"]))
         say("    rows per level %s; operator complexity %.3f" % (" -> ".join(str(L["rows"]) for L in res["levels"]), res["operator_complexity"]))
         for k, L in enumerate(res["levels"]):
             if L["status"] is not None:
                 st, sec = L["status"], L["seconds"]
                 say("    level %2d: %9d rows, %10d entries -> %9d aggregates in %2d rounds, largest %d, %d singletons; aggregate %.4f s, plan %.4f s, "
-                    "symbolic %.4f s, numeric %.4f s" % (k, L["rows"], L["stored_entries"], st[0], st[1], st[2], st[3], sec["aggregate"], sec["plan"],
-                                                         sec["symbolic"], sec["numeric"]))
+                    "symbolic %.4f s, numeric %.4f s%s" % (k, L["rows"], L["stored_entries"], st[0], st[1], st[2], st[3], sec["aggregate"], sec["plan"],
+                                                           sec["symbolic"], sec["numeric"], "; group %d" % L["group"] if args.mis2 else ""))
         say("    setup, all levels: aggregate %.4f s, plan %.4f s, symbolic %.4f s, numeric %.4f s; the hierarchy with its allocations %.4f s" % (
             res["setup_seconds"]["aggregate"], res["setup_seconds"]["plan"], res["setup_seconds"]["symbolic"], res["setup_seconds"]["numeric"],
             res["hierarchy_seconds"]))
@@ -351,6 +398,12 @@ def main():
                     t, u["restrict"], g["restrict_GBps"], u["torch_index_add"], g["restrict_over_torch"], g["restrict_over_triad_by_bytes"],
                     u["prolong_add"], g["prolong_GBps"], u["torch_add_gather"], g["prolong_over_torch"], g["prolong_over_triad_by_bytes"], u["triad"],
                     g["triad_GBps"], g["triad_is"], g["index_dtype"]))
+            if "group" in g:
+                say("    %s: restrict_group at %d lanes %7.1f us (%.1f GB/s) / restrict = %.3f, by bytes beside the triad %.3f (target 1.16: %s; restrict "
+                    "%.3f: %s); max |restrict_group - restrict| %.3e" % (
+                        t, g["group"], u["restrict_group"], g["restrict_group_GBps"], g["restrict_group_over_restrict"], g["restrict_group_over_triad_by_bytes"],
+                        g["restrict_group_target_1.16"], g["restrict_over_triad_by_bytes"], g["restrict_target_1.16"],
+                        g["restrict_group_against_restrict_max_abs"]))
         if "pcg" in res:
             say("    the cycle's levels %s, the coarsest by %s; its plans, smoothers and tables: %.4f s" % (
                 " -> ".join(str(n) for n in res["cycle_levels"]), res["coarsest"], res["cycle_setup_seconds"]))
@@ -359,6 +412,14 @@ def main():
                 extra = ", with the set-up %8.4f s" % (g["seconds"] + setup) if way.startswith("v_cycle") else ""
                 say("        pcg %-18s %6d iterations, %8.4f s%s, r'r / r0'r0 %.3e%s" % (
                     way, g["iterations"], g["seconds"], extra, g["relative_rr"], "" if g["reached"] else " (not reached)"))
+        one = res.get("distance_1")
+        if one and "pcg" in one:
+            say("    the distance-1 cycle in the same process: levels %s, the coarsest by %s; the hierarchy %.4f s, its plans, smoothers and tables "
+                "%.4f s" % (" -> ".join(str(n) for n in one["cycle_levels"]), one["coarsest"], one["hierarchy_seconds"], one["cycle_setup_seconds"]))
+            setup = one["hierarchy_seconds"] + one["cycle_setup_seconds"]
+            for way, g in one["pcg"].items():
+                say("        pcg distance-1 %-18s %6d iterations, %8.4f s, with the set-up %8.4f s, r'r / r0'r0 %.3e%s" % (
+                    way, g["iterations"], g["seconds"], g["seconds"] + setup, g["relative_rr"], "" if g["reached"] else " (not reached)"))
         say(json.dumps(res))
     log.close()
 
