@@ -2,7 +2,8 @@
 // a group of lanes per aggregate): one level of a plain aggregation multigrid over caller-owned device arrays.  The kernels are
 // agg_kernels.hpp; the check of a call's arrays is the conjugate-gradient step's (krylov_check.hpp); the stable sorts are
 // hipCUB's radix sort and the prefix sums spmv_hip_internal_exclusive_scan_i32 (coo_sort.hip), whose temporary memory is
-// allocated and freed inside the three calls that synchronise anyway.
+// allocated and freed inside the three calls that synchronise anyway.  The rounds of both aggregations are those of
+// graph_rounds.hpp, driven by graph_rounds() of krylov_check.hpp, inside one body for the two entry points.
 #include "spmv_hip_agg_mis2.h"
 
 #include "krylov_check.hpp"
@@ -18,20 +19,21 @@ namespace {
 
 typedef struct spmv_hip_agg_plan Plan;
 
-size_t up16(size_t b) { return (b + 15) & ~(size_t) 15; }
-
-// The workspace, cut the same way by the three setup calls: [counter 16][marks: rows bytes][four arrays of rows + 1 ints: the
-// state / the sorted keys, the flags / the row numbers, the ranks, the counts][thresholds: rows doubles] and, for the Galerkin
-// product, [keys: nnz + 2 of 8 bytes, behind the sort the flags and their sums][sorted keys: nnz of 8 bytes][positions: nnz ints]
+// The workspace, cut the same way by the three setup calls: [counters 16: decided, missing][marks: rows bytes][four arrays of
+// rows + 1 ints: the state / the sorted keys, the flags / the row numbers, the ranks, the counts][thresholds: rows doubles] and,
+// for the Galerkin product, [keys: nnz + 2 of 8 bytes, behind the sort the flags and their sums][sorted keys: nnz of 8 bytes]
+// [positions: nnz ints].  The distance-2 aggregation (spmv_hip_agg_mis2_workspace) has [beside: rows bytes] behind the marks, and
+// in the second of the four arrays the nearest keys, then the flags, then the roots joined in pass 1.
 struct Work {
-    size_t counter, marks, ints[4], thresh, key, sorted, idx, bytes;
+    size_t counter, marks, beside, ints[4], thresh, key, sorted, idx, bytes;
 };
-Work work_of(long long rows, long long nnz)
+Work work_of(long long rows, long long nnz, bool mis2 = false)
 {
     Work w;
     w.counter = 0;
     w.marks = 16;
-    size_t at = w.marks + up16((size_t) rows);
+    w.beside = w.marks + up16((size_t) rows);
+    size_t at = w.beside + (mis2 ? up16((size_t) rows) : 0);
     for (int k = 0; k < 4; ++k) {
         w.ints[k] = at;
         at += up16(((size_t) rows + 1) * 4);
@@ -51,7 +53,11 @@ Work work_of(long long rows, long long nnz)
     return w;
 }
 
-unsigned blocks_of(long long threads) { return (unsigned) ((threads + 255) / 256); }
+// out <- the exclusive prefix sums of the n ints of in
+int scan(const int * in, int * out, long long n, hipStream_t s, const char * what)
+{
+    return spmv_hip_internal_exclusive_scan_i32(in, out, n, s) != 0 ? fail(SPMV_HIP_ERR_HIP, what) : SPMV_HIP_OK;
+}
 
 // bits that hold every key below `keys`
 int bits_of(unsigned long long keys)
@@ -80,8 +86,10 @@ int sort_pairs(const K * key_in, K * key_out, const int * value_in, int * value_
     return e == hipSuccess ? SPMV_HIP_OK : fail_hip(e, "the radix sort of the aggregation");
 }
 
-int agg_aggregate(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta, uint32_t seed,
-                  int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
+// spmv_hip_agg_aggregate and, with mis2, spmv_hip_agg_aggregate_mis2: the two differ in the workspace's rule, in the kernels of a
+// round and in how the rows join the roots; the missing counter and its error are the distance-2 call's alone
+int agg_aggregate(bool mis2, int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta,
+                  uint32_t seed, int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
 {
     if (rows < 0)
         return fail(SPMV_HIP_ERR_INVALID, "rows < 0");
@@ -89,7 +97,7 @@ int agg_aggregate(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_col
         return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_value may be null)");
     if (!std::isfinite(theta) || !(theta >= 0.0) || !(theta <= 1.0))
         return fail(SPMV_HIP_ERR_INVALID, "theta is not inside [0, 1]");
-    const Work w = work_of(rows, 0);
+    const Work w = work_of(rows, 0, mis2);
     const KrylovArray arrays[] = {{d_row_ptr, ((unsigned long long) rows + 1) * 4, false, 4, "d_row_ptr"},
                                   {d_column_index, 4, false, 4, "d_column_index"},
                                   {d_value, 8, false, 8, "d_value"},
@@ -99,7 +107,7 @@ int agg_aggregate(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_col
     int rc = krylov_check_arrays(rows, 4, arrays, (int) (sizeof arrays / sizeof arrays[0]));
     if (rc != 0)
         return rc;
-    rc = krylov_check_work(work_bytes, w.bytes, "rows", "spmv_hip_agg_workspace(rows, 0)");
+    rc = krylov_check_work(work_bytes, w.bytes, "rows", mis2 ? "spmv_hip_agg_mis2_workspace(rows)" : "spmv_hip_agg_workspace(rows, 0)");
     if (rc != 0)
         return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -110,45 +118,64 @@ int agg_aggregate(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_col
     }
     char * work = static_cast<char *>(d_work);
     int * decided = reinterpret_cast<int *>(work + w.counter);
+    int * missing = decided + 1;
     unsigned char * mark = reinterpret_cast<unsigned char *>(work + w.marks);
+    unsigned char * beside = reinterpret_cast<unsigned char *>(work + w.beside);
     int * state = reinterpret_cast<int *>(work + w.ints[0]);
-    int * flag = reinterpret_cast<int *>(work + w.ints[1]);
+    int * near = reinterpret_cast<int *>(work + w.ints[1]); // in the rounds; then the flags of the roots; then the roots joined in pass 1
+    int * flag = near, * joined = near;
     int * rank = reinterpret_cast<int *>(work + w.ints[2]);
     int * count = reinterpret_cast<int *>(work + w.ints[3]);
     const double * thresh = d_value && theta > 0.0 ? reinterpret_cast<double *>(work + w.thresh) : nullptr;
-    const unsigned grid = blocks_of(rows > 4 ? rows : 4);
-    hipLaunchKernelGGL(spmv::agg_init_kernel, dim3(grid), dim3(256), 0, s, (int) rows, d_row_ptr, d_column_index, d_value, theta, state,
-                       const_cast<double *>(thresh), d_status);
+    const dim3 g(blocks_of(rows > 4 ? rows : 4)), b(256);
+    const int n = rows;
+    const unsigned key = seed;
+    hipLaunchKernelGGL(spmv::agg_init_kernel, g, b, 0, s, n, d_row_ptr, d_column_index, d_value, theta, state, const_cast<double *>(thresh), d_status);
     HIP_TRY(hipGetLastError());
-    long long left = rows;
     int rounds = 0;
-    while (left > 0) {
-        HIP_TRY(hipMemsetAsync(decided, 0, 4, s));
-        hipLaunchKernelGGL(spmv::agg_mark_kernel, dim3(grid), dim3(256), 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh,
-                           state, mark);
+    rc = graph_rounds(rows, decided, s, "an aggregation round that decided no row: the arrays are not those of a CSR matrix", [&]() -> int {
+        if (mis2) {
+            hipLaunchKernelGGL(spmv::agg_mis2_near_kernel, g, b, 0, s, n, key, d_row_ptr, d_column_index, d_value, thresh, state, near);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(spmv::agg_mis2_mark_kernel, g, b, 0, s, n, key, d_row_ptr, d_column_index, d_value, thresh, state, near, mark);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(spmv::agg_mis2_beside_kernel, g, b, 0, s, n, d_row_ptr, d_column_index, d_value, thresh, mark, beside);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(spmv::agg_mis2_assign_kernel, g, b, 0, s, n, d_row_ptr, d_column_index, d_value, thresh, state, mark, beside, decided);
+        } else {
+            hipLaunchKernelGGL(spmv::rounds_mark_kernel<false>, g, b, 0, s, n, key, d_row_ptr, d_column_index, d_value, thresh, state, mark, (int *) nullptr);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(spmv::agg_assign_kernel, g, b, 0, s, n, d_row_ptr, d_column_index, d_value, thresh, state, mark, decided);
+        }
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(spmv::agg_assign_kernel, dim3(grid), dim3(256), 0, s, (int) rows, d_row_ptr, d_column_index, d_value, thresh, state, mark,
-                           decided);
-        HIP_TRY(hipGetLastError());
-        int got = 0;
-        HIP_TRY(hipMemcpyAsync(&got, decided, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (got <= 0 || got > left) // the largest remaining key always wins: arrays that changed under the call, or not a CSR matrix
-            return fail(SPMV_HIP_ERR_STATE, "an aggregation round that decided no row: the arrays are not those of a CSR matrix");
-        left -= got;
-        ++rounds;
-    }
-    hipLaunchKernelGGL(spmv::agg_flag_kernel, dim3(blocks_of((long long) rows + 1)), dim3(256), 0, s, (int) rows, state, flag);
+        return SPMV_HIP_OK;
+    }, &rounds);
+    if (rc != 0)
+        return rc;
+    hipLaunchKernelGGL(spmv::agg_flag_kernel, dim3(blocks_of((long long) rows + 1)), b, 0, s, n, state, flag);
     HIP_TRY(hipGetLastError());
-    if (spmv_hip_internal_exclusive_scan_i32(flag, rank, (long long) rows + 1, s) != 0)
-        return fail(SPMV_HIP_ERR_HIP, "the prefix sum over the roots");
+    rc = scan(flag, rank, (long long) rows + 1, s, "the prefix sum over the roots");
+    if (rc != 0)
+        return rc;
     HIP_TRY(hipMemsetAsync(count, 0, (size_t) rows * 4, s));
-    hipLaunchKernelGGL(spmv::agg_join_kernel, dim3(grid), dim3(256), 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh,
-                       state, rank, d_agg, count);
+    if (mis2) {
+        HIP_TRY(hipMemsetAsync(missing, 0, 4, s));
+        hipLaunchKernelGGL(spmv::agg_mis2_join1_kernel, g, b, 0, s, n, key, d_row_ptr, d_column_index, d_value, thresh, state, joined);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(spmv::agg_mis2_join2_kernel, g, b, 0, s, n, key, d_row_ptr, d_column_index, d_value, thresh, state, joined, rank, d_agg, count,
+                           missing);
+    } else {
+        hipLaunchKernelGGL(spmv::agg_join_kernel, g, b, 0, s, n, key, d_row_ptr, d_column_index, d_value, thresh, state, rank, d_agg, count);
+    }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(spmv::agg_status_kernel, dim3(grid), dim3(256), 0, s, (int) rows, rounds, rank, count, d_status);
+    hipLaunchKernelGGL(spmv::agg_status_kernel, g, b, 0, s, n, rounds, rank, count, d_status);
     HIP_TRY(hipGetLastError());
+    int none = 0;
+    if (mis2)
+        HIP_TRY(hipMemcpyAsync(&none, missing, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (none != 0)
+        return fail(SPMV_HIP_ERR_STATE, "a covered row without a neighbour that joined a root: the arrays changed under the call");
     return SPMV_HIP_OK;
 }
 
@@ -199,8 +226,9 @@ int agg_plan(int32_t rows, const int32_t * d_agg, const int32_t * d_status, int3
         HIP_TRY(hipStreamSynchronize(s));
         if (off != 0)
             return fail(SPMV_HIP_ERR_STATE, "d_agg holds a number outside 0 ... aggregates - 1");
-        if (spmv_hip_internal_exclusive_scan_i32(count, d_member_ptr, (long long) aggregates + 1, s) != 0)
-            return fail(SPMV_HIP_ERR_HIP, "the prefix sum over the aggregates");
+        rc = scan(count, d_member_ptr, (long long) aggregates + 1, s, "the prefix sum over the aggregates");
+        if (rc != 0)
+            return rc;
         rc = sort_pairs<int>(d_agg, sorted, idx, d_member, rows, bits_of((unsigned long long) aggregates), s);
         if (rc != 0)
             return rc;
@@ -276,8 +304,9 @@ int agg_symbolic(const Plan * plan, int32_t nnz, const int32_t * d_row_ptr, cons
             return rc;
         hipLaunchKernelGGL(spmv::agg_head_kernel, dim3(blocks_of((long long) nnz + 1)), dim3(256), 0, s, nnz, sorted, flag);
         HIP_TRY(hipGetLastError());
-        if (spmv_hip_internal_exclusive_scan_i32(flag, at, (long long) nnz + 1, s) != 0)
-            return fail(SPMV_HIP_ERR_HIP, "the prefix sum over the coarse entries");
+        rc = scan(flag, at, (long long) nnz + 1, s, "the prefix sum over the coarse entries");
+        if (rc != 0)
+            return rc;
         hipLaunchKernelGGL(spmv::agg_pattern_kernel, dim3(blocks_of((long long) nnz + 1)), dim3(256), 0, s, nnz, aggregates, sorted, at,
                            d_coarse_row_ptr, d_coarse_column_index, d_entry_ptr, d_status);
         HIP_TRY(hipGetLastError());
@@ -347,116 +376,6 @@ int agg_restrict(const Plan * plan, const T * d_r, T * d_rc, void * stream)
 
 // ---- include/spmv_hip_agg_mis2.h ---------------------------------------------------------------------------------------------------
 
-// The workspace of the distance-2 aggregation: [counters 16: decided, missing][marks: rows bytes][beside: rows bytes][four arrays
-// of rows + 1 ints: the state, the nearest keys / the flags / the roots joined in pass 1, the ranks, the counts][thresholds: rows
-// doubles]
-struct Work2 {
-    size_t counter, marks, beside, ints[4], thresh, bytes;
-};
-Work2 work2_of(long long rows)
-{
-    Work2 w;
-    w.counter = 0;
-    w.marks = 16;
-    w.beside = w.marks + up16((size_t) rows);
-    size_t at = w.beside + up16((size_t) rows);
-    for (int k = 0; k < 4; ++k) {
-        w.ints[k] = at;
-        at += up16(((size_t) rows + 1) * 4);
-    }
-    w.thresh = at;
-    at += up16((size_t) rows * 8);
-    w.bytes = at;
-    return w;
-}
-
-int agg_aggregate_mis2(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta, uint32_t seed,
-                       int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
-{
-    if (rows < 0)
-        return fail(SPMV_HIP_ERR_INVALID, "rows < 0");
-    if (!d_row_ptr || !d_column_index || !d_agg || !d_status || !d_work)
-        return fail(SPMV_HIP_ERR_INVALID, "null device pointer (only d_value may be null)");
-    if (!std::isfinite(theta) || !(theta >= 0.0) || !(theta <= 1.0))
-        return fail(SPMV_HIP_ERR_INVALID, "theta is not inside [0, 1]");
-    const Work2 w = work2_of(rows);
-    const KrylovArray arrays[] = {{d_row_ptr, ((unsigned long long) rows + 1) * 4, false, 4, "d_row_ptr"},
-                                  {d_column_index, 4, false, 4, "d_column_index"},
-                                  {d_value, 8, false, 8, "d_value"},
-                                  {d_agg, (unsigned long long) rows * 4, true, 4, "d_agg"},
-                                  {d_status, 16, true, 4, "d_status"},
-                                  {d_work, w.bytes, true, 16, "d_work"}};
-    int rc = krylov_check_arrays(rows, 4, arrays, (int) (sizeof arrays / sizeof arrays[0]));
-    if (rc != 0)
-        return rc;
-    rc = krylov_check_work(work_bytes, w.bytes, "rows", "spmv_hip_agg_mis2_workspace(rows)");
-    if (rc != 0)
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (rows == 0) {
-        HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return SPMV_HIP_OK;
-    }
-    char * work = static_cast<char *>(d_work);
-    int * decided = reinterpret_cast<int *>(work + w.counter);
-    int * missing = decided + 1;
-    unsigned char * mark = reinterpret_cast<unsigned char *>(work + w.marks);
-    unsigned char * beside = reinterpret_cast<unsigned char *>(work + w.beside);
-    int * state = reinterpret_cast<int *>(work + w.ints[0]);
-    int * near = reinterpret_cast<int *>(work + w.ints[1]); // in the rounds; then the flags of the roots; then the roots joined in pass 1
-    int * flag = near, * joined = near;
-    int * rank = reinterpret_cast<int *>(work + w.ints[2]);
-    int * count = reinterpret_cast<int *>(work + w.ints[3]);
-    const double * thresh = d_value && theta > 0.0 ? reinterpret_cast<double *>(work + w.thresh) : nullptr;
-    const unsigned grid = blocks_of(rows > 4 ? rows : 4);
-    const dim3 g(grid), b(256);
-    hipLaunchKernelGGL(spmv::agg_init_kernel, g, b, 0, s, (int) rows, d_row_ptr, d_column_index, d_value, theta, state, const_cast<double *>(thresh),
-                       d_status);
-    HIP_TRY(hipGetLastError());
-    long long left = rows;
-    int rounds = 0;
-    while (left > 0) {
-        HIP_TRY(hipMemsetAsync(decided, 0, 4, s));
-        hipLaunchKernelGGL(spmv::agg_mis2_near_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, near);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(spmv::agg_mis2_mark_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, near,
-                           mark);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(spmv::agg_mis2_beside_kernel, g, b, 0, s, (int) rows, d_row_ptr, d_column_index, d_value, thresh, mark, beside);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(spmv::agg_mis2_assign_kernel, g, b, 0, s, (int) rows, d_row_ptr, d_column_index, d_value, thresh, state, mark, beside,
-                           decided);
-        HIP_TRY(hipGetLastError());
-        int got = 0;
-        HIP_TRY(hipMemcpyAsync(&got, decided, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (got <= 0 || got > left) // the largest remaining key always wins: arrays that changed under the call, or not a CSR matrix
-            return fail(SPMV_HIP_ERR_STATE, "an aggregation round that decided no row: the arrays are not those of a CSR matrix");
-        left -= got;
-        ++rounds;
-    }
-    hipLaunchKernelGGL(spmv::agg_flag_kernel, dim3(blocks_of((long long) rows + 1)), b, 0, s, (int) rows, state, flag);
-    HIP_TRY(hipGetLastError());
-    if (spmv_hip_internal_exclusive_scan_i32(flag, rank, (long long) rows + 1, s) != 0)
-        return fail(SPMV_HIP_ERR_HIP, "the prefix sum over the roots");
-    HIP_TRY(hipMemsetAsync(count, 0, (size_t) rows * 4, s));
-    HIP_TRY(hipMemsetAsync(missing, 0, 4, s));
-    hipLaunchKernelGGL(spmv::agg_mis2_join1_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, joined);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(spmv::agg_mis2_join2_kernel, g, b, 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_value, thresh, state, joined,
-                       rank, d_agg, count, missing);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(spmv::agg_status_kernel, g, b, 0, s, (int) rows, rounds, rank, count, d_status);
-    HIP_TRY(hipGetLastError());
-    int none = 0;
-    HIP_TRY(hipMemcpyAsync(&none, missing, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (none != 0)
-        return fail(SPMV_HIP_ERR_STATE, "a covered row without a neighbour that joined a root: the arrays changed under the call");
-    return SPMV_HIP_OK;
-}
-
 bool group_ok(int32_t group) { return group >= 1 && group <= spmv::kWave && (group & (group - 1)) == 0; }
 
 template <class T, int G>
@@ -486,14 +405,10 @@ int agg_restrict_group(const Plan * plan, int32_t group, const T * d_r, T * d_rc
     if (plan->rows == 0)
         return SPMV_HIP_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (group) {
-    case 2: launch_group<T, 2>(plan, d_r, d_rc, s); break;
-    case 4: launch_group<T, 4>(plan, d_r, d_rc, s); break;
-    case 8: launch_group<T, 8>(plan, d_r, d_rc, s); break;
-    case 16: launch_group<T, 16>(plan, d_r, d_rc, s); break;
-    case 32: launch_group<T, 32>(plan, d_r, d_rc, s); break;
-    default: launch_group<T, 64>(plan, d_r, d_rc, s); break;
-    }
+    dispatch_group(group, [&](auto G) {
+        if constexpr (G() >= 2) // (a group of one lane went to agg_restrict above)
+            launch_group<T, G()>(plan, d_r, d_rc, s);
+    });
     HIP_TRY(hipGetLastError());
     return SPMV_HIP_OK;
 }
@@ -530,7 +445,7 @@ int spmv_hip_agg_workspace(int32_t rows, int32_t nnz, size_t * bytes)
 int spmv_hip_agg_aggregate(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta,
                            uint32_t seed, int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
 {
-    return agg_aggregate(rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes, stream);
+    return agg_aggregate(false, rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes, stream);
 }
 
 int spmv_hip_agg_plan(int32_t rows, const int32_t * d_agg, const int32_t * d_status, int32_t * d_member_ptr, int32_t * d_member,
@@ -577,14 +492,14 @@ int spmv_hip_agg_mis2_workspace(int32_t rows, size_t * bytes)
 {
     if (rows < 0 || !bytes)
         return fail(SPMV_HIP_ERR_INVALID, "rows < 0, or bytes is null");
-    *bytes = work2_of(rows).bytes;
+    *bytes = work_of(rows, 0, true).bytes;
     return SPMV_HIP_OK;
 }
 
 int spmv_hip_agg_aggregate_mis2(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, const double * d_value, double theta,
                                 uint32_t seed, int32_t * d_agg, int32_t * d_status, void * d_work, size_t work_bytes, void * stream)
 {
-    return agg_aggregate_mis2(rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes, stream);
+    return agg_aggregate(true, rows, d_row_ptr, d_column_index, d_value, theta, seed, d_agg, d_status, d_work, work_bytes, stream);
 }
 
 int spmv_hip_agg_restrict_group_f64(const struct spmv_hip_agg_plan * plan, int32_t group, const double * d_r, double * d_rc, void * stream)

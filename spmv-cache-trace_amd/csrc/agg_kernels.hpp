@@ -13,19 +13,21 @@
 // barrier, no atomics, no scratch.
 //
 // The aggregation, the member lists and the Galerkin product are one-time code: a lane per row or per entry, integer atomics for
-// the counters only.
+// the counters only.  The key of a row, the walk over its strong neighbours, the largest key among them, the count per wave and
+// the marks of a distance-1 round (rounds_mark_kernel, which does not count here) are graph_rounds.hpp's, shared with the
+// colouring of mcgs_kernels.hpp.
 //
 // include/spmv_hip_agg_mis2.h adds, at the end of this file, agg_restrict_group_kernel<T, G> -- G = 2 ... 64 lanes per aggregate
 // that stride its member list and meet in group_sum<G> -- and the six one-time kernels of the aggregation by a distance-2
 // independent set: four per round (the nearest undecided key, the marks, who is beside a mark, the states) and the two passes in
-// which rows join roots.
+// which rows join roots, all on the walk of graph_rounds.hpp.
 #pragma once
 
-#include "cg_updates.hpp"
+#include "graph_rounds.hpp"
 
 namespace spmv {
 
-constexpr int kAggUndecided = -1, kAggCovered = -2, kAggRoot = -3;
+constexpr int kAggCovered = -2, kAggRoot = -3; // beside kUndecided
 constexpr int kAggRestrictChunk = 256; // aggregates per wave in the restriction
 
 typedef int agg_i4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -46,31 +48,6 @@ struct AggQuad<float> {
 
 // ---- the aggregation -------------------------------------------------------------------------------------------------------------
 
-// the murmur3 finaliser in 32 bits: the key of spmv_hip_mcgs.h
-__device__ __forceinline__ unsigned agg_fmix32(unsigned h)
-{
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-// whether the stored entry e of row i makes its column a neighbour (the column is not i: the caller has looked)
-__device__ __forceinline__ bool agg_strong(const double * __restrict__ value, const double * __restrict__ thresh, int e, long long i)
-{
-    return !thresh || __builtin_fabs(value[e]) >= thresh[i];
-}
-
-// the number of lanes of the wave with `yes`, added to *counter by one lane; every lane of the wave calls it
-__device__ __forceinline__ void agg_wave_count(bool yes, int * __restrict__ counter)
-{
-    const unsigned long long m = __ballot(yes);
-    if (m != 0 && ((int) threadIdx.x & (kWave - 1)) == (int) __builtin_ctzll(m))
-        atomicAdd(counter, __popcll(m));
-}
-
 // state <- undecided, status <- {0, 0, 0, 0}, thresh[i] <- fl(theta max_{k != i} |a_ik|) where there is one
 __global__ __launch_bounds__(256) void agg_init_kernel(int rows, const int * __restrict__ row_ptr, const int * __restrict__ column_index,
                                                        const double * __restrict__ value, double theta, int * __restrict__ state,
@@ -81,7 +58,7 @@ __global__ __launch_bounds__(256) void agg_init_kernel(int rows, const int * __r
         status[i] = 0;
     if (i >= rows)
         return;
-    state[i] = kAggUndecided;
+    state[i] = kUndecided;
     if (!thresh)
         return;
     double m = 0.0;
@@ -94,30 +71,6 @@ __global__ __launch_bounds__(256) void agg_init_kernel(int rows, const int * __r
     thresh[i] = theta * m;
 }
 
-// mark[i] <- 1 where row i is undecided and its key is above the key of every undecided neighbour
-__global__ __launch_bounds__(256) void agg_mark_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr, const int * __restrict__ column_index,
-                                                       const double * __restrict__ value, const double * __restrict__ thresh,
-                                                       const int * __restrict__ state, unsigned char * __restrict__ mark)
-{
-    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
-    if (i >= rows)
-        return;
-    bool win = state[i] == kAggUndecided;
-    if (win) {
-        const unsigned hi = agg_fmix32((unsigned) i ^ seed);
-        const int end = row_ptr[i + 1];
-        for (int e = row_ptr[i]; e < end && win; ++e) {
-            const int j = column_index[e];
-            if (j == (int) i || state[j] != kAggUndecided || !agg_strong(value, thresh, e, i))
-                continue;
-            const unsigned hj = agg_fmix32((unsigned) j ^ seed);
-            if (hj > hi || (hj == hi && j > (int) i))
-                win = false;
-        }
-    }
-    mark[i] = win ? 1 : 0;
-}
-
 // A marked row becomes a root; an undecided row that is not marked and has a neighbour that is a root or marked becomes covered.
 // What a row reads of another does not depend on whether that row has been written yet: a marked row counts by its mark, and a
 // row that is not marked is no root before this launch and none behind it.  *decided += the rows that left the undecided.
@@ -127,21 +80,20 @@ __global__ __launch_bounds__(256) void agg_assign_kernel(int rows, const int * _
 {
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     int to = 0;
-    if (i < rows && state[i] == kAggUndecided) {
+    if (i < rows && state[i] == kUndecided) {
         if (mark[i]) {
             to = kAggRoot;
         } else {
-            const int end = row_ptr[i + 1];
-            for (int e = row_ptr[i]; e < end && to == 0; ++e) {
-                const int j = column_index[e];
-                if (j != (int) i && agg_strong(value, thresh, e, i) && (mark[j] || state[j] == kAggRoot))
+            for_neighbours({row_ptr, column_index, value, thresh}, (int) i, [&](int j) {
+                if (mark[j] || state[j] == kAggRoot)
                     to = kAggCovered;
-            }
+                return to == 0;
+            });
         }
         if (to != 0)
             state[i] = to;
     }
-    agg_wave_count(to != 0, decided);
+    wave_count(to != 0, decided);
 }
 
 // flag[i] <- 1 for a root, flag[rows] <- 0: its exclusive prefix sums are the roots' numbers, and the aggregates behind the last
@@ -152,7 +104,15 @@ __global__ __launch_bounds__(256) void agg_flag_kernel(int rows, const int * __r
         flag[i] = i < rows && state[i] == kAggRoot;
 }
 
-// agg[i] <- the number of the root row i joins: itself, or the root among its neighbours with the largest key; count[agg[i]] += 1
+// the root that row i joins at distance 1: itself, or the root among its neighbours with the largest key; -1 without one
+__device__ __forceinline__ int agg_root_beside(const Neighbours & g, unsigned seed, const int * __restrict__ state, int i)
+{
+    if (state[i] == kAggRoot)
+        return i;
+    return best_by_key(g, seed, i, -1, [&](int j) { return state[j] == kAggRoot ? j : -1; });
+}
+
+// agg[i] <- the number of the root row i joins (agg_root_beside); count[agg[i]] += 1
 __global__ __launch_bounds__(256) void agg_join_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr, const int * __restrict__ column_index,
                                                        const double * __restrict__ value, const double * __restrict__ thresh,
                                                        const int * __restrict__ state, const int * __restrict__ rank, int * __restrict__ agg,
@@ -161,22 +121,7 @@ __global__ __launch_bounds__(256) void agg_join_kernel(int rows, unsigned seed, 
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     if (i >= rows)
         return;
-    int root = (int) i;
-    if (state[i] != kAggRoot) {
-        root = -1;
-        unsigned hr = 0;
-        const int end = row_ptr[i + 1];
-        for (int e = row_ptr[i]; e < end; ++e) {
-            const int j = column_index[e];
-            if (j == (int) i || state[j] != kAggRoot || !agg_strong(value, thresh, e, i))
-                continue;
-            const unsigned hj = agg_fmix32((unsigned) j ^ seed);
-            if (root < 0 || hj > hr || (hj == hr && j > root)) {
-                root = j;
-                hr = hj;
-            }
-        }
-    }
+    const int root = agg_root_beside({row_ptr, column_index, value, thresh}, seed, state, (int) i);
     const int a = root >= 0 ? rank[root] : 0; // (a covered row has a root beside it)
     agg[i] = a;
     atomicAdd(count + a, 1);
@@ -193,7 +138,7 @@ __global__ __launch_bounds__(256) void agg_status_kernel(int rows, int rounds, c
         status[1] = rounds;
     }
     int c = i < aggregates ? count[i] : 0;
-    agg_wave_count(c == 1, status + 3);
+    wave_count(c == 1, status + 3);
 #pragma unroll
     for (int d = kWave / 2; d >= 1; d >>= 1)
         c = max(c, __shfl_xor(c, d));
@@ -216,7 +161,7 @@ __global__ __launch_bounds__(256) void agg_count_kernel(int rows, int aggregates
         if (!off)
             atomicAdd(count + a, 1);
     }
-    agg_wave_count(off, bad);
+    wave_count(off, bad);
 }
 
 // ---- the Galerkin product ----------------------------------------------------------------------------------------------------------
@@ -523,12 +468,6 @@ __global__ __launch_bounds__(256, 8) void agg_restrict_group_kernel(int aggregat
 
 // ---- the aggregation by a distance-2 independent set (include/spmv_hip_agg_mis2.h) -------------------------------------------------
 
-// whether the key of row a (its hash ha) is above the key of row b
-__device__ __forceinline__ bool agg_key_above(unsigned ha, int a, unsigned hb, int b)
-{
-    return ha > hb || (ha == hb && a > b);
-}
-
 // near[i] <- the undecided row of {i} + N(i) with the largest key, -1 without one: every row relays, whatever its state
 __global__ __launch_bounds__(256) void agg_mis2_near_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr,
                                                             const int * __restrict__ column_index, const double * __restrict__ value,
@@ -538,20 +477,8 @@ __global__ __launch_bounds__(256) void agg_mis2_near_kernel(int rows, unsigned s
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     if (i >= rows)
         return;
-    int best = state[i] == kAggUndecided ? (int) i : -1;
-    unsigned hb = agg_fmix32((unsigned) i ^ seed);
-    const int end = row_ptr[i + 1];
-    for (int e = row_ptr[i]; e < end; ++e) {
-        const int j = column_index[e];
-        if (j == (int) i || state[j] != kAggUndecided || !agg_strong(value, thresh, e, i))
-            continue;
-        const unsigned hj = agg_fmix32((unsigned) j ^ seed);
-        if (best < 0 || agg_key_above(hj, j, hb, best)) {
-            best = j;
-            hb = hj;
-        }
-    }
-    near[i] = best;
+    near[i] = best_by_key({row_ptr, column_index, value, thresh}, seed, (int) i, state[i] == kUndecided ? (int) i : -1,
+                          [&](int j) { return state[j] == kUndecided ? j : -1; });
 }
 
 // mark[i] <- 1 where row i is undecided and no near[j], j in {i} + N(i), has a key above its own: the largest within two steps
@@ -563,18 +490,15 @@ __global__ __launch_bounds__(256) void agg_mis2_mark_kernel(int rows, unsigned s
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     if (i >= rows)
         return;
-    bool win = state[i] == kAggUndecided && near[i] == (int) i;
+    bool win = state[i] == kUndecided && near[i] == (int) i;
     if (win) {
-        const unsigned hi = agg_fmix32((unsigned) i ^ seed);
-        const int end = row_ptr[i + 1];
-        for (int e = row_ptr[i]; e < end && win; ++e) {
-            const int j = column_index[e];
-            if (j == (int) i || !agg_strong(value, thresh, e, i))
-                continue;
+        const unsigned hi = fmix32((unsigned) i ^ seed);
+        for_neighbours({row_ptr, column_index, value, thresh}, (int) i, [&](int j) {
             const int n = near[j];
-            if (n >= 0 && agg_key_above(agg_fmix32((unsigned) n ^ seed), n, hi, (int) i))
+            if (n >= 0 && key_above(fmix32((unsigned) n ^ seed), n, hi, (int) i))
                 win = false;
-        }
+            return win;
+        });
     }
     mark[i] = win ? 1 : 0;
 }
@@ -588,11 +512,11 @@ __global__ __launch_bounds__(256) void agg_mis2_beside_kernel(int rows, const in
     if (i >= rows)
         return;
     bool yes = mark[i] != 0;
-    const int end = row_ptr[i + 1];
-    for (int e = row_ptr[i]; e < end && !yes; ++e) {
-        const int j = column_index[e];
-        yes = j != (int) i && agg_strong(value, thresh, e, i) && mark[j] != 0;
-    }
+    if (!yes)
+        for_neighbours({row_ptr, column_index, value, thresh}, (int) i, [&](int j) {
+            yes = mark[j] != 0;
+            return !yes;
+        });
     beside[i] = yes ? 1 : 0;
 }
 
@@ -605,23 +529,22 @@ __global__ __launch_bounds__(256) void agg_mis2_assign_kernel(int rows, const in
 {
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     int to = 0;
-    if (i < rows && state[i] == kAggUndecided) {
+    if (i < rows && state[i] == kUndecided) {
         if (mark[i]) {
             to = kAggRoot;
         } else if (beside[i]) {
             to = kAggCovered;
         } else {
-            const int end = row_ptr[i + 1];
-            for (int e = row_ptr[i]; e < end && to == 0; ++e) {
-                const int j = column_index[e];
-                if (j != (int) i && agg_strong(value, thresh, e, i) && beside[j])
+            for_neighbours({row_ptr, column_index, value, thresh}, (int) i, [&](int j) {
+                if (beside[j])
                     to = kAggCovered;
-            }
+                return to == 0;
+            });
         }
         if (to != 0)
             state[i] = to;
     }
-    agg_wave_count(to != 0, decided);
+    wave_count(to != 0, decided);
 }
 
 // pass 1: joined[i] <- i for a root, the root among the neighbours with the largest key for a row beside one, else -1
@@ -633,23 +556,7 @@ __global__ __launch_bounds__(256) void agg_mis2_join1_kernel(int rows, unsigned 
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     if (i >= rows)
         return;
-    int root = (int) i;
-    if (state[i] != kAggRoot) {
-        root = -1;
-        unsigned hr = 0;
-        const int end = row_ptr[i + 1];
-        for (int e = row_ptr[i]; e < end; ++e) {
-            const int j = column_index[e];
-            if (j == (int) i || state[j] != kAggRoot || !agg_strong(value, thresh, e, i))
-                continue;
-            const unsigned hj = agg_fmix32((unsigned) j ^ seed);
-            if (root < 0 || agg_key_above(hj, j, hr, root)) {
-                root = j;
-                hr = hj;
-            }
-        }
-    }
-    joined[i] = root;
+    joined[i] = agg_root_beside({row_ptr, column_index, value, thresh}, seed, state, (int) i);
 }
 
 // pass 2: a row that joined nobody in pass 1 joins the root that one of its neighbours joined in pass 1 (a neighbour that is no
@@ -665,29 +572,19 @@ __global__ __launch_bounds__(256) void agg_mis2_join2_kernel(int rows, unsigned 
     bool none = false;
     if (i < rows) {
         int root = joined[i];
-        if (root < 0) {
-            unsigned hr = 0;
-            const int end = row_ptr[i + 1];
-            for (int e = row_ptr[i]; e < end; ++e) {
-                const int j = column_index[e];
-                if (j == (int) i || state[j] == kAggRoot || !agg_strong(value, thresh, e, i))
-                    continue;
+        if (root < 0)
+            root = best_by_key({row_ptr, column_index, value, thresh}, seed, (int) i, -1, [&](int j) {
+                if (state[j] == kAggRoot)
+                    return -1;
                 const int q = joined[j];
-                if (q < 0 || q >= rows)
-                    continue;
-                const unsigned hq = agg_fmix32((unsigned) q ^ seed);
-                if (root < 0 || agg_key_above(hq, q, hr, root)) {
-                    root = q;
-                    hr = hq;
-                }
-            }
-        }
+                return q >= 0 && q < rows ? q : -1;
+            });
         none = root < 0;
         const int a = none ? 0 : rank[root];
         agg[i] = a;
         atomicAdd(count + a, 1);
     }
-    agg_wave_count(none, missing);
+    wave_count(none, missing);
 }
 
 } // namespace spmv

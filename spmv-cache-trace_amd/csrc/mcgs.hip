@@ -1,6 +1,7 @@
 // mcgs.hip -- include/spmv_hip_mcgs.h: the multicolour Gauss-Seidel / SSOR preconditioner over caller-owned device arrays.  The
 // kernels are mcgs_kernels.hpp; the check of a call's arrays, the cut and the workspace rule of the apply's dots are the
 // conjugate-gradient step's (krylov_check.hpp), their reduction is the one of the multiplies with dots (f32_plan.hpp: dots_reduce).
+// The rounds of the colouring are those of graph_rounds.hpp, driven by graph_rounds() of krylov_check.hpp.
 #include "spmv_hip_mcgs.h"
 
 #include "krylov_check.hpp"
@@ -16,7 +17,6 @@ namespace {
 
 constexpr int C = SPMV_HIP_MCGS_MAX_COLOURS;
 
-size_t up16(size_t b) { return (b + 15) & ~(size_t) 15; }
 long long mcgs_chunks(long long rows) { return (rows + spmv::kMcgsChunk - 1) / spmv::kMcgsChunk; }
 
 // The workspace of colour and permute, cut the same way by both: [counter 16][colour_ptr (C + 1) ints][marks: rows bytes]
@@ -37,7 +37,6 @@ Work work_of(long long rows)
     return w;
 }
 
-unsigned blocks_of(long long threads) { return (unsigned) ((threads + 255) / 256); }
 unsigned chunk_blocks(long long rows) { return (unsigned) ((mcgs_chunks(rows) + 3) / 4); }
 
 int mcgs_colour(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_column_index, uint32_t seed, int32_t * d_colour, int32_t * d_status,
@@ -66,23 +65,17 @@ int mcgs_colour(int32_t rows, const int32_t * d_row_ptr, const int32_t * d_colum
     const unsigned grid = blocks_of(rows > 4 ? rows : 4);
     hipLaunchKernelGGL(spmv::mcgs_init_kernel, dim3(grid), dim3(256), 0, s, (int) rows, d_colour, d_status);
     HIP_TRY(hipGetLastError());
-    long long left = rows;
     int rounds = 0;
-    while (left > 0) {
-        HIP_TRY(hipMemsetAsync(winners, 0, 4, s));
-        hipLaunchKernelGGL(spmv::mcgs_mark_kernel, dim3(grid), dim3(256), 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index, d_colour, mark,
-                           winners);
+    rc = graph_rounds(rows, winners, s, "a colouring round without a winner: the arrays are not those of a CSR matrix", [&]() -> int {
+        hipLaunchKernelGGL(spmv::rounds_mark_kernel<true>, dim3(grid), dim3(256), 0, s, (int) rows, (unsigned) seed, d_row_ptr, d_column_index,
+                           (const double *) nullptr, (const double *) nullptr, d_colour, mark, winners);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(spmv::mcgs_assign_kernel, dim3(grid), dim3(256), 0, s, (int) rows, d_row_ptr, d_column_index, d_colour, mark, d_status);
         HIP_TRY(hipGetLastError());
-        int won = 0;
-        HIP_TRY(hipMemcpyAsync(&won, winners, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (won <= 0 || won > left) // the largest remaining key always wins: arrays that changed under the call, or not a CSR matrix
-            return fail(SPMV_HIP_ERR_STATE, "a colouring round without a winner: the arrays are not those of a CSR matrix");
-        left -= won;
-        ++rounds;
-    }
+        return SPMV_HIP_OK;
+    }, &rounds);
+    if (rc != 0)
+        return rc;
     hipLaunchKernelGGL(spmv::mcgs_check_kernel, dim3(grid), dim3(256), 0, s, (int) rows, d_row_ptr, d_column_index, d_colour, rounds, d_status);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -238,15 +231,7 @@ int sweep_colours(const spmv_hip_mcgs_plan * plan, int first, int last, double o
     for (int c = first;; c += step) {
         const int k0 = plan->colour_ptr[c], k1 = plan->colour_ptr[c + 1];
         if (k1 > k0) {
-            switch (plan->group) {
-            case 1: launch_colour<T, 1>(plan, k0, k1, omega, b, minv, x, s); break;
-            case 2: launch_colour<T, 2>(plan, k0, k1, omega, b, minv, x, s); break;
-            case 4: launch_colour<T, 4>(plan, k0, k1, omega, b, minv, x, s); break;
-            case 8: launch_colour<T, 8>(plan, k0, k1, omega, b, minv, x, s); break;
-            case 16: launch_colour<T, 16>(plan, k0, k1, omega, b, minv, x, s); break;
-            case 32: launch_colour<T, 32>(plan, k0, k1, omega, b, minv, x, s); break;
-            default: launch_colour<T, 64>(plan, k0, k1, omega, b, minv, x, s); break;
-            }
+            dispatch_group(plan->group, [&](auto G) { launch_colour<T, G()>(plan, k0, k1, omega, b, minv, x, s); });
             HIP_TRY(hipGetLastError());
         }
         if (c == last)

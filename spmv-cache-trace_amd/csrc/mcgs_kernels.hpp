@@ -11,10 +11,11 @@
 // restrict: it is written by this launch, by other rows' lanes.  No LDS, no barrier, no atomics, no scratch.
 //
 // The colouring, the counting sort and the copy are one-time code: a lane per row (a wave per 1024 rows in the sort), integer
-// atomics for the counters only.
+// atomics for the counters only.  The colouring's key, its walk over a row's neighbours and the marks of a round are
+// graph_rounds.hpp's, shared with the aggregations of agg_kernels.hpp.
 #pragma once
 
-#include "cg_updates.hpp"
+#include "graph_rounds.hpp"
 
 namespace spmv {
 
@@ -24,50 +25,17 @@ constexpr int kMcgsChunk = 1024;    // rows per wave in the counting sort and th
 
 // ---- the colouring ---------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ unsigned mcgs_fmix32(unsigned h)
-{
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-// colour <- -1 (uncoloured), status <- {0, 0, 0, 0}
+// colour <- undecided, status <- {0, 0, 0, 0}
 __global__ __launch_bounds__(256) void mcgs_init_kernel(int rows, int * __restrict__ colour, int * __restrict__ status)
 {
     const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
     if (i < rows)
-        colour[i] = -1;
+        colour[i] = kUndecided;
     if (i < 4)
         status[i] = 0;
 }
 
-// mark[i] <- 1 where row i is uncoloured and its key is above the key of every uncoloured neighbour; *winners += their number
-__global__ __launch_bounds__(256) void mcgs_mark_kernel(int rows, unsigned seed, const int * __restrict__ row_ptr, const int * __restrict__ column_index,
-                                                        const int * __restrict__ colour, unsigned char * __restrict__ mark, int * __restrict__ winners)
-{
-    const long long i = (long long) blockIdx.x * 256 + (int) threadIdx.x;
-    if (i >= rows)
-        return;
-    bool win = colour[i] < 0;
-    if (win) {
-        const unsigned hi = mcgs_fmix32((unsigned) i ^ seed);
-        const int end = row_ptr[i + 1];
-        for (int e = row_ptr[i]; e < end && win; ++e) {
-            const int j = column_index[e];
-            if (j == (int) i || colour[j] >= 0)
-                continue;
-            const unsigned hj = mcgs_fmix32((unsigned) j ^ seed);
-            if (hj > hi || (hj == hi && j > (int) i))
-                win = false;
-        }
-    }
-    mark[i] = win ? 1 : 0;
-    if (win)
-        atomicAdd(winners, 1);
-}
+// (the marks of a round are rounds_mark_kernel's, counted there: graph_rounds.hpp)
 
 // the marked rows take the smallest colour that no neighbour which is NOT marked holds: those rows are not written in this launch
 __global__ __launch_bounds__(256) void mcgs_assign_kernel(int rows, const int * __restrict__ row_ptr, const int * __restrict__ column_index, int * colour,
@@ -77,15 +45,12 @@ __global__ __launch_bounds__(256) void mcgs_assign_kernel(int rows, const int * 
     if (i >= rows || !mark[i])
         return;
     unsigned long long held = 0;
-    const int end = row_ptr[i + 1];
-    for (int e = row_ptr[i]; e < end; ++e) {
-        const int j = column_index[e];
-        if (j == (int) i || mark[j])
-            continue;
-        const int c = colour[j];
+    for_neighbours({row_ptr, column_index, nullptr, nullptr}, (int) i, [&](int j) {
+        const int c = mark[j] ? -1 : colour[j]; // (the colour of a marked row is not even read)
         if (c >= 0)
             held |= 1ULL << (c & 63);
-    }
+        return true;
+    });
     int c = kMcgsMaxColours - 1;
     if (~held == 0)
         atomicAdd(status + 3, 1);
@@ -104,11 +69,10 @@ __global__ __launch_bounds__(256) void mcgs_check_kernel(int rows, const int * _
     int mine = -1, same = 0;
     if (i < rows) {
         mine = colour[i];
-        const int end = row_ptr[i + 1];
-        for (int e = row_ptr[i]; e < end; ++e) {
-            const int j = column_index[e];
-            same += j != (int) i && colour[j] == mine;
-        }
+        for_neighbours({row_ptr, column_index, nullptr, nullptr}, (int) i, [&](int j) {
+            same += colour[j] == mine;
+            return true;
+        });
     }
     // one atomic per wave and counter (a single address takes about 10^8 a second)
 #pragma unroll

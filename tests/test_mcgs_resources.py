@@ -22,14 +22,18 @@ SRC = '#include "mcgs_kernels.hpp"\n' \
       + "".join("template __global__ void spmv::mcgs_sweep_kernel<%s, %d>(int, int, const int *, const int *, const int *, const double *, double, "
                 "double, const %s *, const %s *, %s *);\n" % (t, g, t, t, t) for t in ("double", "float") for g in GROUPS) \
       + "".join("template __global__ void spmv::mcgs_dots_kernel<%s>(long long, const %s *, const %s *, spmv::v2d *);\n" % (t, t, t)
-                for t in ("double", "float"))
+                for t in ("double", "float")) \
+      + "template __global__ void spmv::rounds_mark_kernel<true>(int, unsigned, const int *, const int *, const double *, const double *, const int *, " \
+        "unsigned char *, int *);\n"
 # type: (VGPRs, waves per SIMD) of the seven group sizes
 SHIPPED = {
     "d": [(76, 6), (77, 6), (51, 8), (52, 8), (51, 8), (51, 8), (50, 8)],
     "f": [(63, 8), (65, 7), (48, 8), (49, 8), (48, 8), (48, 8), (47, 8)],
 }
 DOTS = {"d": (40, 8), "f": (64, 8)}
-ONE_TIME = ("init", "mark", "assign", "check", "hist", "offsets", "scatter", "chunk_sum", "chunk_scan", "row_scan", "copy")
+# (the marks of a colouring round are graph_rounds.hpp's rounds_mark_kernel<true>, instantiated above)
+ONE_TIME = ("mcgs_init", "rounds_mark", "mcgs_assign", "mcgs_check", "mcgs_hist", "mcgs_offsets", "mcgs_scatter", "mcgs_chunk_sum", "mcgs_chunk_scan",
+            "mcgs_row_scan", "mcgs_copy")
 
 
 @pytest.fixture(scope="module")
@@ -84,6 +88,6 @@ def test_no_scratch_no_lds_and_the_shipped_registers_in_the_sweep(remarks, t):
 
 def test_the_one_time_kernels_use_no_scratch_and_are_reported(remarks):
     for name in ONE_TIME:
-        remark = _remarks_of(remarks, "mcgs_%s_kernel" % name)
+        remark = _remarks_of(remarks, "%s_kernel" % name)
         _report(name, remark)
         assert remark("ScratchSize [bytes/lane]") == 0
