@@ -1,7 +1,7 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
 spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h,
-spmv_hip_cheby.h, spmv_hip_mcgs.h, spmv_hip_agg.h and spmv_hip_agg_mis2.h (the C ABI of libspmv_hip.so).
+spmv_hip_cheby.h, spmv_hip_mcgs.h, spmv_hip_agg.h, spmv_hip_agg_mis2.h and spmv_hip_coarse.h (the C ABI of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -28,7 +28,8 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                           "spmv_hip_transpose.h", "spmv_hip_f32values.h", "spmv_hip_compact.h",
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
                                           "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h",
-                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h", "spmv_hip_agg.h", "spmv_hip_agg_mis2.h")]
+                                          "spmv_hip_cheby.h", "spmv_hip_mcgs.h", "spmv_hip_agg.h", "spmv_hip_agg_mis2.h",
+                                          "spmv_hip_coarse.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -233,6 +234,13 @@ SIGNATURES = {
     "spmv_hip_agg_restrict_group_f64": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "spmv_hip_agg_restrict_group_f32": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "spmv_hip_agg_group": (C.c_int32, [_vp]),
+    # spmv_hip_coarse.h
+    "spmv_hip_coarse_ld": (C.c_int32, [C.c_int32]),
+    "spmv_hip_coarse_workspace": (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
+    "spmv_hip_coarse_setup_f64": (C.c_int, [C.c_int32] + [_vp] * 6 + [C.c_size_t, _vp]),
+    "spmv_hip_coarse_setup_f32": (C.c_int, [C.c_int32] + [_vp] * 6 + [C.c_size_t, _vp]),
+    "spmv_hip_coarse_apply_f64": (C.c_int, [C.c_int32] + [_vp] * 4),
+    "spmv_hip_coarse_apply_f32": (C.c_int, [C.c_int32] + [_vp] * 4),
 }
 
 
@@ -1447,3 +1455,35 @@ def agg_restrict_group(plan, group, d_r, d_rc, stream=0, dtype=None):
 def agg_group(plan):
     """The recommended group of agg_restrict_group: the smallest power of two >= rows / aggregates inside 1 ... 64; host arithmetic."""
     return int(load().spmv_hip_agg_group(_plan_ref(plan)))
+
+
+COARSE_MAX_N = 2048
+
+
+def coarse_ld(n):
+    """The elements of one row of the inverse of coarse_setup: n rounded up to a multiple of 4, 0 for n <= 0; host arithmetic."""
+    return int(load().spmv_hip_coarse_ld(n))
+
+
+def coarse_workspace_bytes(n):
+    """The workspace of coarse_setup over n rows: a function of n alone, at least 16 (include/spmv_hip_coarse.h)."""
+    b = C.c_size_t(0)
+    check(load().spmv_hip_coarse_workspace(n, C.byref(b)))
+    return b.value
+
+
+def coarse_setup(n, d_row_ptr, d_column_index, d_value, d_inv, d_status, d_work, work_bytes=None, stream=0, dtype=None):
+    """d_inv (n rows of coarse_ld(n) elements, row-major) <- the inverse of the n x n device CSR matrix (d_value doubles) by
+    Gauss-Jordan with partial pivoting, the identity where it is singular; d_status (three int32) <- {singular, the first column
+    with a zero pivot or -1, entries skipped for their column} (include/spmv_hip_coarse.h).  Torch tensors or raw device addresses;
+    the inverse is float64 or float32 by the dtype of d_inv (a raw address: dtype=); work_bytes defaults to the size of a tensor
+    d_work.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_coarse_setup_" + _krylov_suffix((d_inv,), dtype))
+    check(fn(n, _addr(d_row_ptr), _addr(d_column_index), _addr(d_value), _addr(d_inv), _addr(d_status), _addr(d_work),
+             _work_bytes(d_work, work_bytes), stream))
+
+
+def coarse_apply(n, d_inv, d_r, d_z, stream=0, dtype=None):
+    """z <- inv r for the dense inverse of coarse_setup, a wave per row.  Arguments as for cg_step.  Only enqueues."""
+    fn = getattr(load(), "spmv_hip_coarse_apply_" + _krylov_suffix((d_inv, d_r, d_z), dtype))
+    check(fn(n, _addr(d_inv), _addr(d_r), _addr(d_z), stream))

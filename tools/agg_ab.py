@@ -25,12 +25,19 @@ target of the counted bytes at the triad's rate x 1.16 ("met" / "missed"); in `p
 dense coarsest solve and the grouped restriction on every level, at omega 1, 1.5 and 2, and then the distance-1 cycle above built
 and run in the same process.  The log goes to profiles/agg_mis2_ab.log.
 
+--coarse library (include/spmv_hip_coarse.h; the default, torch, leaves every recorded figure as it was): the coarsest level of
+every matrix is set up by spmv_hip_coarse_setup_f64 and applied by spmv_hip_coarse_apply_f64.  In place of `transfer` the log holds,
+for that level, the set-up against torch.linalg.inv of the dense matrix (which the host formed for it) and the apply against torch's
+matrix-vector product, alternating; in `pcg` every V-cycle runs with the library's solve and with torch's, alternating, without the
+baselines and without the distance-1 cycle.  The log goes to profiles/coarse_ab.log.
+
 Three warm-up rounds, then --rounds rounds alternating the ways, medians.  The log goes to stdout and to profiles/agg_ab.log
 (--log).
 
     python tools/agg_ab.py
     python tools/agg_ab.py --only poisson_4096 --rounds 25 --no-pcg
     python tools/agg_ab.py --mis2
+    python tools/agg_ab.py --mis2 --coarse library
 """
 import argparse
 import json
@@ -166,21 +173,67 @@ def transfer(torch, capi, L, rounds, s):
     return out
 
 
-def prepare_cycle(torch, capi, levels, dense_limit, coarse_degree, s):
+def library_inverse(torch, capi, L, s):
+    """(inv, status, work) of spmv_hip_coarse_setup_f64 on the level's device arrays; only enqueued."""
+    dev = L.tp.device
+    inv = torch.zeros(max(1, L.n * capi.coarse_ld(L.n)), dtype=torch.float64, device=dev)
+    status = torch.zeros(3, dtype=torch.int32, device=dev)
+    work = torch.zeros(capi.coarse_workspace_bytes(L.n) // 8, dtype=torch.float64, device=dev)
+    capi.coarse_setup(L.n, L.tp, L.tc, L.tv, inv, status, work, None, s)
+    return inv, status, work
+
+
+def dense_of(torch, L):
+    """The level's matrix as a dense device tensor, formed on the host."""
+    import scipy.sparse as sp
+    p_h, c_h, v_h = L.tp.cpu().numpy(), L.tc.cpu().numpy()[:L.nnz], L.tv.cpu().numpy()[:L.nnz]
+    return torch.from_numpy(sp.csr_matrix((v_h, c_h, p_h), shape=(L.n, L.n)).toarray()).to(L.tp.device)
+
+
+def coarse_ab(torch, capi, L, rounds, s):
+    """The dense solve of the coarsest level by the library and by torch, alternating: the set-up from the level's device CSR arrays
+    against torch.linalg.inv of the dense matrix (formed on the host beforehand, outside the timing), the apply against
+    torch.matmul(inverse, r, out=z)."""
+    n, dev = L.n, L.tp.device
+    dense = dense_of(torch, L)
+    inv, status, work = library_inverse(torch, capi, L, s)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(9)
+    r = torch.rand(n, generator=gen, dtype=torch.float64, device=dev) * 2 - 1
+    z, zt = torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev)
+    kept = {}
+
+    def torch_inv():
+        kept["inverse"] = torch.linalg.inv(dense)
+
+    setup = alternate(torch, {"library": lambda: capi.coarse_setup(n, L.tp, L.tc, L.tv, inv, status, work, None, s), "torch": torch_inv}, rounds)
+    apply = alternate(torch, {"library": lambda: capi.coarse_apply(n, inv, r, z, s),
+                              "torch": lambda: torch.matmul(kept["inverse"], r, out=zt)}, rounds)
+    eye = torch.eye(n, dtype=torch.float64, device=dev)
+    mine = inv.view(n, capi.coarse_ld(n))[:, :n]
+    return {"rows": n, "launches_of_setup": 2 * n + 3, "status": status.cpu().numpy().tolist(),
+            "setup_ms": {k: round(v / 1e3, 4) for k, v in setup.items()}, "apply_us": {k: round(v, 2) for k, v in apply.items()},
+            "setup_library_over_torch": round(setup["library"] / setup["torch"], 3), "apply_library_over_torch": round(apply["library"] / apply["torch"], 3),
+            "max_abs_AX_minus_I": {"library": float((dense @ mine - eye).abs().max()), "torch": float((dense @ kept["inverse"] - eye).abs().max())},
+            "z_max_abs_difference": float((z - zt).abs().max()), "z_max_abs": float(zt.abs().max())}
+
+
+def prepare_cycle(torch, capi, levels, dense_limit, coarse_degree, s, coarse="torch"):
     """Per level: a C16Plan, minv, the degree-2 table over [lambda / 4, lambda] and the cycle's vectors.  The last level is solved by
     its dense inverse where it has at most dense_limit rows, else by a FIXED Chebyshev polynomial of coarse_degree over [lambda /
-    RATIO, lambda] (a fixed symmetric operator, so CG stays valid; not a solve)."""
-    import scipy.sparse as sp
+    RATIO, lambda] (a fixed symmetric operator, so CG stays valid; not a solve).  coarse == "library": the inverse by
+    spmv_hip_coarse_setup_f64 beside torch's (the level has at most SPMV_HIP_COARSE_MAX_N rows, or this raises); L.way says which
+    of the two the cycle applies."""
     dev = levels[0].tp.device
     i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
     for k, L in enumerate(levels):
         n = L.n
         L.r, L.z = torch.zeros(n, **f64), torch.zeros(n, **f64)
-        L.inverse = None
+        L.inverse, L.way = None, "torch"
         if k == len(levels) - 1 and n <= dense_limit:
-            p_h, c_h, v_h = L.tp.cpu().numpy(), L.tc.cpu().numpy()[:L.nnz], L.tv.cpu().numpy()[:L.nnz]
-            dense = sp.csr_matrix((v_h, c_h, p_h), shape=(n, n)).toarray()
-            L.inverse = torch.linalg.inv(torch.from_numpy(dense).to(dev))
+            L.inverse = torch.linalg.inv(dense_of(torch, L))
+            if coarse == "library":
+                L.inv, L.inv_status, L.inv_work = library_inverse(torch, capi, L, s)
             continue
         p_h, c_h = L.tp.cpu().numpy(), np.ascontiguousarray(L.tc.cpu().numpy()[:L.nnz])
         L.c16 = capi.C16Plan(n, n, p_h, c_h, 0, s)
@@ -208,7 +261,9 @@ def v_cycle(torch, capi, levels, omega, coarse_degree, s):
     def cycle(k, r, z):
         L = levels[k]
         if k == len(levels) - 1:
-            if L.inverse is not None:
+            if L.way == "library":
+                capi.coarse_apply(L.n, L.inv, r, z, s)
+            elif L.inverse is not None:
                 torch.matmul(L.inverse, r, out=z)
             else:
                 polynomial(L, coarse_degree, L.coarse_table, r, z)
@@ -229,7 +284,7 @@ def v_cycle(torch, capi, levels, omega, coarse_degree, s):
     return lambda src, z: cycle(0, src, z)
 
 
-def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s, omegas=(1.0, 1.5), baselines=True):
+def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s, omegas=(1.0, 1.5), baselines=True, coarse_ways=("torch",)):
     top = levels[0]
     n, dev = top.n, rhs.device
     f64 = dict(dtype=torch.float64, device=dev)
@@ -254,17 +309,19 @@ def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s, omegas=(1.0, 1.5)
             capi.cheby_step(n, 3, j, table, src if j == 0 else u, minv, d, z, src if last else None, dots if last else None,
                             kwork if last else None, None, s)
 
-    def cycle_at(omega):
+    def cycle_at(omega, way):
         run = v_cycle(torch, capi, levels, omega, coarse_degree, s)
 
         def apply(src, dots):
+            levels[-1].way = way
             run(src, z)
             dots[0:1].copy_(torch.dot(src, z).reshape(1))
 
         return apply
 
     out = {}
-    ways = ([("diagonal", diagonal), ("chebyshev_3", chebyshev)] if baselines else []) + [("v_cycle_omega_%.1f" % w, cycle_at(w)) for w in omegas]
+    ways = ([("diagonal", diagonal), ("chebyshev_3", chebyshev)] if baselines else []) \
+        + [("v_cycle_omega_%.1f%s" % (w, "" if coarse_ways == ("torch",) else "_" + way), cycle_at(w, way)) for w in omegas for way in coarse_ways]
     for way, apply in ways:
         x.zero_()
         r.copy_(rhs)
@@ -292,7 +349,8 @@ def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s, omegas=(1.0, 1.5)
     return out
 
 
-def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, omegas=(1.0, 1.5), baselines=True):
+def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, omegas=(1.0, 1.5), baselines=True,
+               coarse="torch"):
     """PCG with the V-cycle over `levels` into res: the cycle's levels, its set-up and res["pcg"]."""
     # the cycle's levels: down to the floor, or to the first level that the aggregation shrinks by less than --stall
     depth = 0
@@ -302,20 +360,21 @@ def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_li
     if depth == 0:
         return
     t0 = time.perf_counter()
-    prepare_cycle(torch, capi, used, dense_limit, coarse_degree, s)
+    prepare_cycle(torch, capi, used, dense_limit, coarse_degree, s, coarse)
     res["cycle_setup_seconds"] = round(time.perf_counter() - t0, 4)
     res["cycle_levels"] = [L.n for L in used]
-    res["coarsest"] = "dense inverse" if used[-1].inverse is not None else "Chebyshev polynomial of degree %d over [lambda / %g, lambda]" % (coarse_degree, RATIO)
+    library = coarse == "library" and used[-1].inverse is not None
+    res["coarsest"] = "the library's dense inverse and torch's, alternating" if library else "dense inverse" if used[-1].inverse is not None else "Chebyshev polynomial of degree %d over [lambda / %g, lambda]" % (coarse_degree, RATIO)
     gen = torch.Generator(device=levels[0].tp.device)
     gen.manual_seed(9)
     rhs = torch.rand(rows, generator=gen, dtype=torch.float64, device=levels[0].tp.device) * 2 - 1
-    res["pcg"] = pcg(torch, capi, used, rhs, cap, look, coarse_degree, s, omegas, baselines)
+    res["pcg"] = pcg(torch, capi, used, rhs, cap, look, coarse_degree, s, omegas, baselines, ("library", "torch") if library else ("torch",))
     for L in used:
         if L.inverse is None:
             L.c16.close()
 
 
-def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degree, solve, mis2=False):
+def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degree, solve, mis2=False, coarse="torch"):
     import torch
     from spmv_amd import capi
     dev = torch.device("cuda:0")
@@ -334,11 +393,14 @@ def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degr
                       "group": L.group} for L in levels]
     res["operator_complexity"] = round(sum(L.nnz for L in levels) / max(1, nnz), 3)
     res["setup_seconds"] = {k: round(sum(L.seconds[k] for L in levels if L.plan is not None), 4) for k in ("aggregate", "plan", "symbolic", "numeric")}
-    if levels[0].plan is not None:
+    if coarse == "library":
+        res["coarse"] = coarse_ab(torch, capi, levels[-1], rounds, s)
+    elif levels[0].plan is not None:
         res["transfer"] = transfer(torch, capi, levels[0], rounds, s)
     if solve and len(levels) > 1:
-        solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, (1.0, 1.5, 2.0) if mis2 else (1.0, 1.5))
-        if mis2:
+        solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, (1.0, 1.5, 2.0) if mis2 else (1.0, 1.5),
+                   coarse == "torch", coarse)
+        if mis2 and coarse == "torch":
             # the distance-1 cycle of DESIGN 3.24 in the same process, its hierarchy and set-up timed the same way
             del levels
             torch.cuda.synchronize()
@@ -363,9 +425,11 @@ def main():
     ap.add_argument("--no-pcg", action="store_true")
     ap.add_argument("--mis2", action="store_true", help="the distance-2 aggregates and the grouped restriction of spmv_hip_agg_mis2.h; the log "
                     "goes to profiles/agg_mis2_ab.log")
+    ap.add_argument("--coarse", choices=("torch", "library"), default="torch", help="who solves the coarsest level: torch.linalg.inv and torch's "
+                    "matrix-vector product, or spmv_hip_coarse_setup_f64 and spmv_hip_coarse_apply_f64 beside them; the log goes to profiles/coarse_ab.log")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
-    log = open(args.log or os.path.join(ROOT, "profiles", "agg_mis2_ab.log" if args.mis2 else "agg_ab.log"), "w")
+    log = open(args.log or os.path.join(ROOT, "profiles", "coarse_ab.log" if args.coarse == "library" else "agg_mis2_ab.log" if args.mis2 else "agg_ab.log"), "w")
 
     def say(text):
         print(text, flush=True)
@@ -375,11 +439,14 @@ def main():
     say("plain aggregation (theta 0, seed 0%s) down to <= %d rows; restriction and prolongation against torch and beside the triad; one process, torch "
         "events on one stream, 3 warm-up rounds, then %d rounds alternating the ways, medians" % (
             ", distance-2 roots, spmv_hip_agg_group(plan) lanes per aggregate in the grouped restriction" if args.mis2 else "", args.floor, args.rounds))
+    if args.coarse == "library":
+        say("--coarse library: the coarsest level by spmv_hip_coarse_setup_f64 and spmv_hip_coarse_apply_f64 against torch.linalg.inv and torch.matmul, "
+            "alternating, in place of the transfers; PCG with each, without the baselines and the distance-1 cycle")
     for name, spec, what, spd in MATRICES:
         if args.only and name not in args.only:
             continue
         res = matrix(name, spec, args.rounds, args.cap, args.look, args.floor, args.stall, args.dense_limit, args.coarse_degree, spd and not args.no_pcg,
-                     args.mis2)
+                     args.mis2, args.coarse)
         say("%-13s %s: %d rows, %d stored entries; %s" % (name, what, res["rows"], res["stored_entries"], res["library"]))
         say("    rows per level %s; operator complexity %.3f" % (" -> ".join(str(L["rows"]) for L in res["levels"]), res["operator_complexity"]))
         for k, L in enumerate(res["levels"]):
@@ -404,6 +471,13 @@ def main():
                         t, g["group"], u["restrict_group"], g["restrict_group_GBps"], g["restrict_group_over_restrict"], g["restrict_group_over_triad_by_bytes"],
                         g["restrict_group_target_1.16"], g["restrict_over_triad_by_bytes"], g["restrict_target_1.16"],
                         g["restrict_group_against_restrict_max_abs"]))
+        if "coarse" in res:
+            g = res["coarse"]
+            say("    the coarsest level, %d rows: set-up (%d launches) %.3f ms / torch.linalg.inv %.3f ms = %.3f; apply %.1f us / torch.matmul %.1f us = "
+                "%.3f; max |A X - I| %.3e against %.3e; max |z - z_torch| %.3e of max |z| %.3e; status %s" % (
+                    g["rows"], g["launches_of_setup"], g["setup_ms"]["library"], g["setup_ms"]["torch"], g["setup_library_over_torch"],
+                    g["apply_us"]["library"], g["apply_us"]["torch"], g["apply_library_over_torch"], g["max_abs_AX_minus_I"]["library"],
+                    g["max_abs_AX_minus_I"]["torch"], g["z_max_abs_difference"], g["z_max_abs"], g["status"]))
         if "pcg" in res:
             say("    the cycle's levels %s, the coarsest by %s; its plans, smoothers and tables: %.4f s" % (
                 " -> ".join(str(n) for n in res["cycle_levels"]), res["coarsest"], res["cycle_setup_seconds"]))
