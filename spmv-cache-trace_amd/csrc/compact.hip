@@ -2,13 +2,18 @@
 // (include/spmv_hip_compact_f64.h) and y <- fl32(y + fl32(A) x) on float x and y (include/spmv_hip_compact_f32xy.h), with the columns of a tile as 16-bit codes (a 3-bit window number and a 13-bit offset from one of
 // eight per-tile bases).  The tiles are f32values.hip's own (f32_plan.hpp): its descriptors as they
 // are, with the compact bits and the tile's first code quad added; the bases and the codes are made on the host by a few
-// threads, tile by tile; the kernel is csr_compact.hpp.  The multiplies' refusals and launches are tile_front.hpp's: this file
+// threads, tile by tile -- or, for arrays that are on the device already (include/spmv_hip_compact_device.h), by the two kernels
+// of c16_plan_kernels.hpp; the kernel is csr_compact.hpp.  The multiplies' refusals and launches are tile_front.hpp's: this file
 // describes its three families to it (C16Family).  Level 1 of formats 7 to 10 is here too, once for both plans: the upload
 // (upload_float_tile) and the multiply of a context on its own arrays (ctx_tile_multiply).
 #include "tile_front.hpp"
 #include "csr_compact.hpp"
+#include "c16_plan_kernels.hpp"
+#include "spmv_hip_compact_device.h"
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <atomic>
 #include <new>
@@ -74,6 +79,36 @@ int code_tile(const int32_t * col, int32_t k0, int32_t k1, int32_t * base, uint1
     return nw;
 }
 
+// What the host planner and the device planner share once every tile's windows (0 = wide) are known: the compact bits and the
+// first code quad into the descriptors, the counts, the plan's bytes; quads: the length of the code stream.
+int finish_descriptors(spmv_hip_c16_plan & pl, std::vector<int4> & desc, const int32_t * windows, long long f32_streamed_bytes, long long & quads)
+{
+    const int nt = pl.ntiles;
+    quads = 0;
+    for (int w = 0; w < nt; ++w) {
+        int4 & d = desc[(size_t) w];
+        const int32_t k0 = d.y, k1 = desc[(size_t) w + 1].y, kb = k0 & ~3;
+        const int nw = windows[(size_t) w];
+        if (nw == 0) {
+            ++pl.wide_tiles;
+            continue;
+        }
+        if (quads > 0xFFFFFFFFLL)
+            return fail(SPMV_HIP_ERR_OVERFLOW, "the code stream is too long for a 32-bit quad index");
+        d.z |= spmv::kC16MetaCompact | (nw == 1 ? spmv::kC16MetaOneWindow : 0);
+        d.w = (int) (unsigned) quads;
+        if (k1 > k0)
+            quads += ((k1 - 1 - kb) >> 2) + 1;
+        ++pl.compact_tiles;
+        pl.compact_entries += k1 - k0;
+        ++pl.windows_hist[nw - 1];
+    }
+    pl.device_bytes = (16 * ((size_t) nt + 1) + 32 * (size_t) nt + 8 * (size_t) quads + 15) & ~(size_t) 15;
+    // the fp32-value plan's bytes with 2 instead of 4 bytes of column per compact entry, and the bases
+    pl.streamed_bytes = f32_streamed_bytes - 2LL * pl.compact_entries + 32LL * nt;
+    return SPMV_HIP_OK;
+}
+
 int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, const int32_t * col, unsigned flags)
 {
     spmv_hip_c16_plan & pl = hp.numbers;
@@ -135,24 +170,8 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
         return fail(SPMV_HIP_ERR_ALLOC, "compact plan: host memory");
     // the compact bits and the first code quad into the descriptors, and the device layout of the codes
     long long quads = 0;
-    for (int w = 0; w < nt; ++w) {
-        int4 & d = hp.desc[(size_t) w];
-        const int32_t k0 = d.y, k1 = hp.desc[(size_t) w + 1].y, kb = k0 & ~3;
-        const int nw = hp.windows[(size_t) w];
-        if (nw == 0) {
-            ++pl.wide_tiles;
-            continue;
-        }
-        if (quads > 0xFFFFFFFFLL)
-            return fail(SPMV_HIP_ERR_OVERFLOW, "the code stream is too long for a 32-bit quad index");
-        d.z |= spmv::kC16MetaCompact | (nw == 1 ? spmv::kC16MetaOneWindow : 0);
-        d.w = (int) (unsigned) quads;
-        if (k1 > k0)
-            quads += ((k1 - 1 - kb) >> 2) + 1;
-        ++pl.compact_tiles;
-        pl.compact_entries += k1 - k0;
-        ++pl.windows_hist[nw - 1];
-    }
+    if ((rc = finish_descriptors(pl, hp.desc, hp.windows.data(), fp.numbers.streamed_bytes, quads)) != 0)
+        return rc;
     hp.codes.assign(4 * (size_t) quads, 0);
     for (int w = 0; w < nt; ++w)
         if (hp.windows[(size_t) w] > 0) {
@@ -161,9 +180,6 @@ int plan_host(HostPlan & hp, int32_t rows, int32_t cols, const int32_t * p, cons
                 std::memcpy(&hp.codes[4 * (size_t) (unsigned) hp.desc[(size_t) w].w + (size_t) (k0 & 3)], &hp.by_entry[(size_t) k0],
                             (size_t) (k1 - k0) * sizeof(uint16_t));
         }
-    pl.device_bytes = (16 * ((size_t) nt + 1) + 32 * (size_t) nt + 8 * (size_t) quads + 15) & ~(size_t) 15;
-    // the fp32-value plan's bytes with 2 instead of 4 bytes of column per compact entry, and the bases
-    pl.streamed_bytes = fp.numbers.streamed_bytes - 2LL * pl.compact_entries + 32LL * nt;
     return SPMV_HIP_OK;
 }
 
@@ -209,6 +225,135 @@ int build_plan(spmv_hip_c16_plan ** out, HostPlan const & hp, hipStream_t s)
         if (e != hipSuccess) {
             spmv_hip_c16_plan_destroy(pl);
             return fail_hip(e, "compact plan: descriptors, bases and codes");
+        }
+        pl->d_desc = reinterpret_cast<const int4 *>(pl->d_all);
+        pl->d_bases = reinterpret_cast<const int *>(pl->d_all + desc_bytes);
+        pl->d_codes = reinterpret_cast<const uint16_t *>(pl->d_all + desc_bytes + base_bytes);
+    }
+    *out = pl;
+    return SPMV_HIP_OK;
+}
+
+// ---- the plan from device arrays (include/spmv_hip_compact_device.h): row_ptr to the host for f32_plan_host's tiles, the columns
+// to c16_plan_kernels.hpp's two kernels where they are ------------------------------------------------------------------------------
+
+// a device allocation of one call, freed where the call returns
+struct DeviceTemp {
+    char * p = nullptr;
+    ~DeviceTemp()
+    {
+        if (p)
+            (void) hipFree(p);
+    }
+};
+
+// Wall-clock seconds of the stages of the last spmv_hip_c16_plan_csr_device, for tools/agg_ab.py: {row_ptr copy, tile cut, windows
+// kernel, codes kernel, the rest}.  Only libspmv_hip_experiments.so keeps them, and it waits for the stream between the stages
+// to do so; in the product library this is nothing.
+struct StageClock {
+#ifdef SPMV_HIP_EXPERIMENTS
+    static double seconds[5];
+    hipStream_t s;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit StageClock(hipStream_t stream) : s(stream) { std::fill(seconds, seconds + 5, 0.0); }
+    void done(int stage)
+    {
+        (void) hipStreamSynchronize(s);
+        const auto t1 = std::chrono::steady_clock::now();
+        seconds[stage] += std::chrono::duration<double>(t1 - t0).count();
+        t0 = t1;
+    }
+#else
+    explicit StageClock(hipStream_t) {}
+    void done(int) {}
+#endif
+};
+#ifdef SPMV_HIP_EXPERIMENTS
+double StageClock::seconds[5] = {0.0};
+#endif
+
+int out_of_range(long long count)
+{
+    char text[160];
+    std::snprintf(text, sizeof text, "%lld column index(es) out of range [0, cols)", count);
+    return fail(SPMV_HIP_ERR_INVALID, text);
+}
+
+// spmv_hip_c16_plan_csr_device behind the refusals that need no device; throws std::bad_alloc
+int plan_device(spmv_hip_c16_plan ** out, int32_t rows, int32_t cols, const int32_t * d_row_ptr, const int32_t * d_col, unsigned flags,
+                hipStream_t s)
+{
+    StageClock clock(s);
+    std::vector<int32_t> p((size_t) rows + 1);
+    HIP_TRY(hipMemcpyAsync(p.data(), d_row_ptr, p.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    clock.done(0);
+    int rc = f32_check_host(rows, cols, p.data(), flags);
+    if (rc != 0)
+        return rc;
+    const int32_t nnz = p[(size_t) rows];
+    if (nnz > 0 && !d_col)
+        return fail(SPMV_HIP_ERR_INVALID, "d_column_index is null");
+    if (nnz > 0 && cols == 0)
+        return out_of_range(nnz); // no column lies in [0, 0)
+    F32HostPlan fp;
+    f32_plan_host(fp, rows, cols, p.data(), flags);
+    clock.done(1);
+    spmv_hip_c16_plan numbers;
+    numbers.rows = rows;
+    numbers.cols = cols;
+    numbers.nnz = nnz;
+    numbers.flags = flags;
+    const int nt = numbers.ntiles = fp.numbers.ntiles;
+    numbers.long_tiles = fp.numbers.long_tiles;
+    long long quads = 0;
+    DeviceTemp temp;
+    const size_t desc_bytes = ((size_t) nt + 1) * sizeof(int4), base_bytes = 8 * (size_t) nt * sizeof(int32_t);
+    if (nt > 0) {
+        // the descriptors as cut, room for the bases, the count of columns out of range, a window count per tile
+        std::vector<int32_t> windows((size_t) nt);
+        unsigned long long bad = 0;
+        HIP_TRY(hipMalloc((void **) &temp.p, desc_bytes + base_bytes + 16 + (size_t) nt * sizeof(int32_t)));
+        unsigned long long * d_bad = reinterpret_cast<unsigned long long *>(temp.p + desc_bytes + base_bytes);
+        int * d_windows = reinterpret_cast<int *>(temp.p + desc_bytes + base_bytes + 16);
+        HIP_TRY(hipMemcpyAsync(temp.p, fp.desc.data(), desc_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof bad, s));
+        clock.done(4);
+        hipLaunchKernelGGL(spmv::c16_windows_kernel, dim3((unsigned) ((nt + 3) / 4)), dim3(256), 0, s, nt, reinterpret_cast<const int4 *>(temp.p),
+                           d_col, (int) cols, reinterpret_cast<int *>(temp.p + desc_bytes), d_windows, d_bad);
+        HIP_TRY(hipGetLastError());
+        clock.done(2);
+        HIP_TRY(hipMemcpyAsync(windows.data(), d_windows, (size_t) nt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (bad > 0)
+            return out_of_range((long long) bad);
+        if ((rc = finish_descriptors(numbers, fp.desc, windows.data(), fp.numbers.streamed_bytes, quads)) != 0)
+            return rc;
+    }
+    spmv_hip_c16_plan * pl = new (std::nothrow) spmv_hip_c16_plan(numbers);
+    if (!pl)
+        return fail(SPMV_HIP_ERR_ALLOC, "plan allocation failed");
+    if (nt > 0) {
+        // the plan's block: the finished descriptors from the host, the bases from the temporary, the codes by the second kernel
+        hipError_t e = hipMalloc((void **) &pl->d_all, pl->device_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(pl->d_all, fp.desc.data(), desc_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(pl->d_all + desc_bytes, temp.p + desc_bytes, base_bytes, hipMemcpyDeviceToDevice, s);
+        clock.done(4);
+        if (e == hipSuccess && quads > 0) {
+            hipLaunchKernelGGL(spmv::c16_codes_kernel, dim3((unsigned) ((nt + 3) / 4)), dim3(256), 0, s, nt, reinterpret_cast<const int4 *>(pl->d_all),
+                               reinterpret_cast<const int *>(pl->d_all + desc_bytes), d_col,
+                               reinterpret_cast<uint16_t *>(pl->d_all + desc_bytes + base_bytes));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        clock.done(3);
+        if (e != hipSuccess) {
+            spmv_hip_c16_plan_destroy(pl);
+            return fail_hip(e, "compact plan from device arrays");
         }
         pl->d_desc = reinterpret_cast<const int4 *>(pl->d_all);
         pl->d_bases = reinterpret_cast<const int *>(pl->d_all + desc_bytes);
@@ -390,6 +535,95 @@ int spmv_hip_c16_plan_csr(spmv_hip_c16_plan ** plan, int32_t rows, int32_t cols,
         return fail(SPMV_HIP_ERR_NO_DEVICE, "no HIP device visible");
     return build_plan(plan, hp, static_cast<hipStream_t>(stream));
 }
+
+int spmv_hip_c16_plan_csr_device(spmv_hip_c16_plan ** plan, int32_t rows, int32_t cols, const int32_t * d_row_ptr,
+                                 const int32_t * d_column_index, unsigned flags, void * stream)
+{
+    if (!plan)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    if (rows < 0 || cols < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "bad CSR arguments (rows < 0 or cols < 0)");
+    if (flags & ~SPMV_HIP_FLAG_EXACT_ORDER)
+        return fail(SPMV_HIP_ERR_INVALID, "unknown flag bits (0 or SPMV_HIP_FLAG_EXACT_ORDER)");
+    if (!d_row_ptr)
+        return fail(SPMV_HIP_ERR_INVALID, "d_row_ptr is null");
+    if ((reinterpret_cast<uintptr_t>(d_row_ptr) | reinterpret_cast<uintptr_t>(d_column_index)) & 3u)
+        return fail(SPMV_HIP_ERR_ALIGN, "d_row_ptr and d_column_index must be 4-byte aligned");
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1)
+        return fail(SPMV_HIP_ERR_NO_DEVICE, "no HIP device visible");
+    try {
+        return plan_device(plan, rows, cols, d_row_ptr, d_column_index, flags, static_cast<hipStream_t>(stream));
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "compact plan from device arrays: host memory");
+    }
+}
+
+int spmv_hip_c16_plan_table(const spmv_hip_c16_plan * pl, int32_t * tile_table, int64_t tile_table_ints, uint16_t * codes, int64_t codes_len,
+                            void * stream)
+{
+    if (!pl)
+        return fail(SPMV_HIP_ERR_INVALID, "plan is null");
+    if (tile_table_ints < 0 || codes_len < 0)
+        return fail(SPMV_HIP_ERR_INVALID, "a negative count");
+    const int nt = pl->ntiles;
+    if (tile_table && (long long) SPMV_HIP_C16_TILE_INTS * nt > tile_table_ints)
+        return fail(SPMV_HIP_ERR_INVALID, "tile_table is too small: it takes 13 int32 values per tile");
+    if (codes && pl->nnz > codes_len)
+        return fail(SPMV_HIP_ERR_INVALID, "codes is too small: it takes one value per stored entry");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (nt == 0 || (!tile_table && !codes)) {
+        if (codes && pl->nnz > 0)
+            std::memset(codes, 0, (size_t) pl->nnz * sizeof(uint16_t));
+        if (pl->d_all)
+            HIP_TRY(hipStreamSynchronize(s));
+        return SPMV_HIP_OK;
+    }
+    try {
+        // the descriptors and the bases always (they say where a tile's codes are), the code stream where the codes are asked for
+        const size_t desc_bytes = ((size_t) nt + 1) * sizeof(int4), base_bytes = 8 * (size_t) nt * sizeof(int32_t),
+                     code_bytes = codes ? pl->device_bytes - desc_bytes - base_bytes : 0;
+        std::vector<int4> desc((size_t) nt + 1);
+        std::vector<int32_t> bases(8 * (size_t) nt);
+        std::vector<uint16_t> stream_codes(code_bytes / sizeof(uint16_t));
+        HIP_TRY(hipMemcpyAsync(desc.data(), pl->d_desc, desc_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(bases.data(), pl->d_bases, base_bytes, hipMemcpyDeviceToHost, s));
+        if (code_bytes > 0)
+            HIP_TRY(hipMemcpyAsync(stream_codes.data(), pl->d_codes, code_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (codes)
+            std::memset(codes, 0, (size_t) pl->nnz * sizeof(uint16_t));
+        for (int w = 0; w < nt; ++w) {
+            const int4 & d = desc[(size_t) w];
+            const bool compact = (d.z & spmv::kC16MetaCompact) != 0;
+            const int32_t * b = &bases[8 * (size_t) w];
+            if (tile_table) {
+                int32_t * t = tile_table + (size_t) SPMV_HIP_C16_TILE_INTS * w;
+                tile_table_row(t, &d);
+                int nw = compact ? 1 : 0; // ascending bases up to the last window, which the others repeat
+                for (int i = 1; compact && i < SPMV_HIP_C16_WINDOWS; ++i)
+                    nw += b[i] > b[i - 1];
+                t[4] = nw;
+                for (int i = 0; i < SPMV_HIP_C16_WINDOWS; ++i)
+                    t[5 + i] = compact ? b[i] : 0;
+            }
+            const int32_t k0 = d.y, k1 = desc[(size_t) w + 1].y;
+            if (codes && compact && k1 > k0)
+                std::memcpy(codes + k0, &stream_codes[4 * (size_t) (unsigned) d.w + (size_t) (k0 & 3)], (size_t) (k1 - k0) * sizeof(uint16_t));
+        }
+    } catch (std::bad_alloc const &) {
+        return fail(SPMV_HIP_ERR_ALLOC, "compact plan table: host memory");
+    }
+    return SPMV_HIP_OK;
+}
+
+#ifdef SPMV_HIP_EXPERIMENTS
+// not part of the C ABI: the stage times of the last spmv_hip_c16_plan_csr_device of this library (StageClock)
+void spmv_hip_c16_plan_device_times(double * out)
+{
+    std::copy(StageClock::seconds, StageClock::seconds + 5, out);
+}
+#endif
 
 int spmv_hip_csr_spmv_c16(const spmv_hip_c16_plan * pl, const int32_t * d_row_ptr, const int32_t * d_column_index, const float * d_value,
                           const double * d_x, double * d_y, void * stream)

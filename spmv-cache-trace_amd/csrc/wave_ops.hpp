@@ -70,6 +70,17 @@ __device__ __forceinline__ double group_sum(double v)
     return v;
 }
 
+// The smallest int of the wave, in every lane: group_sum<64>'s butterfly over 32-bit moves (every lane active, as there).
+__device__ __forceinline__ int wave_min(int v)
+{
+    v = min(v, __builtin_amdgcn_update_dpp(0, v, kDppQuadXor1, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(0, v, kDppQuadXor2, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(0, v, kDppRowHalfMirror, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_update_dpp(0, v, kDppRowMirror, 0xF, 0xF, false));
+    v = min(v, __builtin_amdgcn_ds_swizzle(v, (16 << 10) | 0x1F));
+    return min(v, __builtin_amdgcn_ds_bpermute(((int) __lane_id() ^ 32) << 2, v));
+}
+
 // Value of lane (lane - d) for d < 64, 0-filled below lane d is NOT implied:
 // callers test lane >= d themselves.
 __device__ __forceinline__ double lane_up(double v, int d)

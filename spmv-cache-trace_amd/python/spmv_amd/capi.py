@@ -1,7 +1,8 @@
 """ctypes binding of include/spmv_hip.h, spmv_hip_tuning.h, spmv_hip_plan.h, spmv_hip_symmetric.h, spmv_hip_multivec.h,
 spmv_hip_transpose.h, spmv_hip_f32values.h, spmv_hip_compact.h, spmv_hip_compact_f64.h, spmv_hip_compact_f32xy.h,
 spmv_hip_scaled.h, spmv_hip_dots.h, spmv_hip_krylov.h, spmv_hip_bicgstab.h, spmv_hip_gmres.h, spmv_hip_bjacobi.h,
-spmv_hip_cheby.h, spmv_hip_mcgs.h, spmv_hip_agg.h, spmv_hip_agg_mis2.h and spmv_hip_coarse.h (the C ABI of libspmv_hip.so).
+spmv_hip_cheby.h, spmv_hip_mcgs.h, spmv_hip_agg.h, spmv_hip_agg_mis2.h, spmv_hip_coarse.h and spmv_hip_compact_device.h (the C ABI
+of libspmv_hip.so).
 
 This is plumbing: it loads the in-tree shared library and turns negative return
 codes into ``SpmvHipError``.  There is deliberately no fallback of any kind: if
@@ -29,7 +30,7 @@ HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(PKG_ROOT), "include
                                           "spmv_hip_compact_f64.h", "spmv_hip_compact_f32xy.h", "spmv_hip_scaled.h", "spmv_hip_dots.h",
                                           "spmv_hip_krylov.h", "spmv_hip_bicgstab.h", "spmv_hip_gmres.h", "spmv_hip_bjacobi.h",
                                           "spmv_hip_cheby.h", "spmv_hip_mcgs.h", "spmv_hip_agg.h", "spmv_hip_agg_mis2.h",
-                                          "spmv_hip_coarse.h")]
+                                          "spmv_hip_coarse.h", "spmv_hip_compact_device.h")]
 
 OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_STATE, ERR_OVERFLOW, ERR_ALIGN = -1, -2, -3, -4, -5, -6, -7
@@ -150,6 +151,8 @@ SIGNATURES = {
     "spmv_hip_c16_plan_verify": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _vp]),
     "spmv_hip_c16_plan_info": (C.c_int, [_vp, _i64p, C.c_int]),
     "spmv_hip_c16_plan_destroy": (None, [_vp]),
+    "spmv_hip_c16_plan_csr_device": (C.c_int, [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, _vp, C.c_uint, _vp]),
+    "spmv_hip_c16_plan_table": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "spmv_hip_upload_csr_compact": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int]),
     "spmv_hip_upload_csr_compact_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "spmv_hip_csr_spmv_c16_f32xy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -906,6 +909,30 @@ class C16Plan:
         self.h = h
         self.rows, self.cols = rows, cols
 
+    @classmethod
+    def from_device(cls, rows, cols, d_row_ptr, d_col, flags=0, stream=0):
+        """The same plan from DEVICE row_ptr and columns (spmv_hip_c16_plan_csr_device; raw addresses or torch tensors), read on
+        `stream` behind whatever wrote them: the columns do not visit the host."""
+        self = cls.__new__(cls)
+        self.lib = load()
+        self.h = None
+        h = _vp()
+        rp, col = ((_dev(a)[0] if a is not None else 0) or None for a in (d_row_ptr, d_col))
+        check(self.lib.spmv_hip_c16_plan_csr_device(C.byref(h), rows, cols, rp, col, flags, stream))
+        self.h = h
+        self.rows, self.cols = rows, cols
+        return self
+
+    def table(self, codes=False, stream=0):
+        """The plan read back in c16_plan_preview's format (spmv_hip_c16_plan_table): the int32 tile table [tiles, 13] and, with
+        codes=True, the uint16 code of every stored entry by entry index (None otherwise)."""
+        info = self.info()
+        tab = np.zeros((info["tiles"], C16_TILE_INTS), dtype=np.int32)
+        cod = np.zeros(info["stored_entries"], dtype=np.uint16) if codes else None
+        check(self.lib.spmv_hip_c16_plan_table(self.h, tab.ctypes.data if tab.size else None, tab.size,
+                                               cod.ctypes.data if codes and cod.size else None, cod.size if codes else 0, stream))
+        return tab, cod
+
     def close(self):
         if self.h:
             self.lib.spmv_hip_c16_plan_destroy(self.h)
@@ -988,6 +1015,20 @@ class C16Plan:
         n = C.c_int64(-1)
         check(self.lib.spmv_hip_c16_plan_verify(self.h, d_col or None, C.byref(n), stream))
         return n.value
+
+
+def c16_plan_device_times():
+    """Timing hook of libspmv_hip_experiments.so (SPMV_HIP_EXPERIMENTS=1), not part of the C ABI: seconds of the stages of the
+    last C16Plan.from_device -- {row_ptr copy, tile cut, windows kernel, codes kernel, the rest} -- or None in the product
+    library, which does not wait between the stages."""
+    lib = load()
+    if not hasattr(lib, "spmv_hip_c16_plan_device_times"):
+        return None
+    out = (C.c_double * 5)()
+    lib.spmv_hip_c16_plan_device_times.argtypes = [C.POINTER(C.c_double)]
+    lib.spmv_hip_c16_plan_device_times.restype = None
+    lib.spmv_hip_c16_plan_device_times(out)
+    return list(out)
 
 
 def narrow_values(n, d_value, d_out, stream=0):

@@ -31,6 +31,12 @@ for that level, the set-up against torch.linalg.inv of the dense matrix (which t
 matrix-vector product, alternating; in `pcg` every V-cycle runs with the library's solve and with torch's, alternating, without the
 baselines and without the distance-1 cycle.  The log goes to profiles/coarse_ab.log.
 
+--plans device (include/spmv_hip_compact_device.h; the default, host, leaves every recorded figure as it was): every C16Plan of the
+cycle by spmv_hip_c16_plan_csr_device from the level's device arrays, no column copied to the host.  --plans both: per level the
+host's way (row_ptr and columns copied down, spmv_hip_c16_plan_csr) against the device's, five rounds alternating after one
+warm-up, medians (under SPMV_HIP_EXPERIMENTS=1 with the stages of the device call), then `pcg` over the host's plans and once more
+over the device's, without the distance-1 cycle.  The log goes to profiles/c16_device_plan_ab.log.
+
 Three warm-up rounds, then --rounds rounds alternating the ways, medians.  The log goes to stdout and to profiles/agg_ab.log
 (--log).
 
@@ -218,8 +224,51 @@ def coarse_ab(torch, capi, L, rounds, s):
             "z_max_abs_difference": float((z - zt).abs().max()), "z_max_abs": float(zt.abs().max())}
 
 
-def prepare_cycle(torch, capi, levels, dense_limit, coarse_degree, s, coarse="torch"):
-    """Per level: a C16Plan, minv, the degree-2 table over [lambda / 4, lambda] and the cycle's vectors.  The last level is solved by
+def plans_ab(torch, capi, levels, s, rounds=5):
+    """Per level with a C16Plan in the cycle: what a set-up pays for its plan today -- row_ptr and the columns copied to the host,
+    then spmv_hip_c16_plan_csr -- against C16Plan.from_device on the arrays where they are; one warm-up, then `rounds` rounds
+    alternating the two, wall clock around a synchronised stream, medians.  The plans are compared by their 20 numbers.  Under
+    SPMV_HIP_EXPERIMENTS=1 the library waits between the stages of the device call and reports them."""
+    out = []
+    for L in levels:
+        n = L.n
+        times = {"host_copy": [], "host_plan": [], "device": []}
+        stages = []
+        for rnd in range(rounds + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            p_h, c_h = L.tp.cpu().numpy(), np.ascontiguousarray(L.tc.cpu().numpy()[:L.nnz])
+            t1 = time.perf_counter()
+            host = capi.C16Plan(n, n, p_h, c_h, 0, s)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            dev = capi.C16Plan.from_device(n, n, L.tp, L.tc, 0, s)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            assert host.info() == dev.info() and dev.verify(L.tc.data_ptr(), s) == 0
+            info = dev.info()
+            host.close()
+            dev.close()
+            if rnd > 0:
+                times["host_copy"].append(t1 - t0)
+                times["host_plan"].append(t2 - t1)
+                times["device"].append(t3 - t2)
+                st = capi.c16_plan_device_times()
+                if st is not None:
+                    stages.append(st)
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        g = {"rows": n, "stored_entries": L.nnz, "tiles": info["tiles"], "wide_tiles": info["wide_tiles"], "ms": {k: round(1e3 * v, 3) for k, v in med.items()},
+             "host_ms": round(1e3 * float(np.median(np.array(times["host_copy"]) + np.array(times["host_plan"]))), 3)}
+        g["device_over_host"] = round(g["ms"]["device"] / g["host_ms"], 3) if g["host_ms"] > 0 else None
+        if stages:
+            g["device_stage_ms"] = dict(zip(("row_ptr_copy", "tile_cut", "windows_kernel", "codes_kernel", "rest"),
+                                            (round(1e3 * float(v), 3) for v in np.median(np.array(stages), axis=0))))
+        out.append(g)
+    return out
+
+
+def prepare_cycle(torch, capi, levels, dense_limit, coarse_degree, s, coarse="torch", plans="host"):
+    """Per level: a C16Plan (plans == "device": by C16Plan.from_device, no column copied to the host), minv, the degree-2 table over [lambda / 4, lambda] and the cycle's vectors.  The last level is solved by
     its dense inverse where it has at most dense_limit rows, else by a FIXED Chebyshev polynomial of coarse_degree over [lambda /
     RATIO, lambda] (a fixed symmetric operator, so CG stays valid; not a solve).  coarse == "library": the inverse by
     spmv_hip_coarse_setup_f64 beside torch's (the level has at most SPMV_HIP_COARSE_MAX_N rows, or this raises); L.way says which
@@ -235,8 +284,11 @@ def prepare_cycle(torch, capi, levels, dense_limit, coarse_degree, s, coarse="to
             if coarse == "library":
                 L.inv, L.inv_status, L.inv_work = library_inverse(torch, capi, L, s)
             continue
-        p_h, c_h = L.tp.cpu().numpy(), np.ascontiguousarray(L.tc.cpu().numpy()[:L.nnz])
-        L.c16 = capi.C16Plan(n, n, p_h, c_h, 0, s)
+        if plans == "device":
+            L.c16 = capi.C16Plan.from_device(n, n, L.tp, L.tc, 0, s)
+        else:  # whose columns go through the host
+            p_h, c_h = L.tp.cpu().numpy(), np.ascontiguousarray(L.tc.cpu().numpy()[:L.nnz])
+            L.c16 = capi.C16Plan(n, n, p_h, c_h, 0, s)
         L.P, L.C, L.A = L.tp.data_ptr(), L.tc.data_ptr(), L.tv.data_ptr()
         L.minv, L.ones = torch.zeros(n, **f64), torch.ones(n, **f64)
         L.bstatus = torch.zeros(2, **i32)
@@ -350,7 +402,7 @@ def pcg(torch, capi, levels, rhs, cap, look, coarse_degree, s, omegas=(1.0, 1.5)
 
 
 def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, omegas=(1.0, 1.5), baselines=True,
-               coarse="torch"):
+               coarse="torch", plans="host"):
     """PCG with the V-cycle over `levels` into res: the cycle's levels, its set-up and res["pcg"]."""
     # the cycle's levels: down to the floor, or to the first level that the aggregation shrinks by less than --stall
     depth = 0
@@ -360,7 +412,8 @@ def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_li
     if depth == 0:
         return
     t0 = time.perf_counter()
-    prepare_cycle(torch, capi, used, dense_limit, coarse_degree, s, coarse)
+    prepare_cycle(torch, capi, used, dense_limit, coarse_degree, s, coarse, plans)
+    res["plans"] = plans
     res["cycle_setup_seconds"] = round(time.perf_counter() - t0, 4)
     res["cycle_levels"] = [L.n for L in used]
     library = coarse == "library" and used[-1].inverse is not None
@@ -374,7 +427,7 @@ def solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_li
             L.c16.close()
 
 
-def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degree, solve, mis2=False, coarse="torch"):
+def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degree, solve, mis2=False, coarse="torch", plans="host"):
     import torch
     from spmv_amd import capi
     dev = torch.device("cuda:0")
@@ -397,10 +450,18 @@ def matrix(name, spec, rounds, cap, look, floor, stall, dense_limit, coarse_degr
         res["coarse"] = coarse_ab(torch, capi, levels[-1], rounds, s)
     elif levels[0].plan is not None:
         res["transfer"] = transfer(torch, capi, levels[0], rounds, s)
+    if plans == "both":
+        res["plans_ab"] = plans_ab(torch, capi, [L for L in levels if L.plan is not None], s)
     if solve and len(levels) > 1:
-        solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, (1.0, 1.5, 2.0) if mis2 else (1.0, 1.5),
-                   coarse == "torch", coarse)
-        if mis2 and coarse == "torch":
+        omegas = (1.0, 1.5, 2.0) if mis2 else (1.0, 1.5)
+        solve_with(torch, capi, levels, res, rows, cap, look, floor, stall, dense_limit, coarse_degree, s, omegas, coarse == "torch", coarse,
+                   "device" if plans == "device" else "host")
+        if plans == "both":
+            # the same cycle once more over plans made on the device: the same bits, so the same iterations; without the baselines
+            res["device_plans"] = {}
+            solve_with(torch, capi, levels, res["device_plans"], rows, cap, look, floor, stall, dense_limit, coarse_degree, s, omegas, False, coarse,
+                       "device")
+        if mis2 and coarse == "torch" and plans == "host":
             # the distance-1 cycle of DESIGN 3.24 in the same process, its hierarchy and set-up timed the same way
             del levels
             torch.cuda.synchronize()
@@ -427,9 +488,13 @@ def main():
                     "goes to profiles/agg_mis2_ab.log")
     ap.add_argument("--coarse", choices=("torch", "library"), default="torch", help="who solves the coarsest level: torch.linalg.inv and torch's "
                     "matrix-vector product, or spmv_hip_coarse_setup_f64 and spmv_hip_coarse_apply_f64 beside them; the log goes to profiles/coarse_ab.log")
+    ap.add_argument("--plans", choices=("host", "device", "both"), default="host", help="who makes the cycle's C16Plans: spmv_hip_c16_plan_csr from "
+                    "arrays copied to the host (the default: every recorded figure as it was), spmv_hip_c16_plan_csr_device from the arrays where they "
+                    "are, or both: per level the two set-ups alternating, then the PCG with each kind of plan; the log goes to "
+                    "profiles/c16_device_plan_ab.log")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
-    log = open(args.log or os.path.join(ROOT, "profiles", "coarse_ab.log" if args.coarse == "library" else "agg_mis2_ab.log" if args.mis2 else "agg_ab.log"), "w")
+    log = open(args.log or os.path.join(ROOT, "profiles", "c16_device_plan_ab.log" if args.plans != "host" else "coarse_ab.log" if args.coarse == "library" else "agg_mis2_ab.log" if args.mis2 else "agg_ab.log"), "w")
 
     def say(text):
         print(text, flush=True)
@@ -446,7 +511,7 @@ def main():
         if args.only and name not in args.only:
             continue
         res = matrix(name, spec, args.rounds, args.cap, args.look, args.floor, args.stall, args.dense_limit, args.coarse_degree, spd and not args.no_pcg,
-                     args.mis2, args.coarse)
+                     args.mis2, args.coarse, args.plans)
         say("%-13s %s: %d rows, %d stored entries; %s" % (name, what, res["rows"], res["stored_entries"], res["library"]))
         say("    rows per level %s; operator complexity %.3f" % (" -> ".join(str(L["rows"]) for L in res["levels"]), res["operator_complexity"]))
         for k, L in enumerate(res["levels"]):
@@ -478,6 +543,19 @@ def main():
                     g["rows"], g["launches_of_setup"], g["setup_ms"]["library"], g["setup_ms"]["torch"], g["setup_library_over_torch"],
                     g["apply_us"]["library"], g["apply_us"]["torch"], g["apply_library_over_torch"], g["max_abs_AX_minus_I"]["library"],
                     g["max_abs_AX_minus_I"]["torch"], g["z_max_abs_difference"], g["z_max_abs"], g["status"]))
+        for k, g in enumerate(res.get("plans_ab", [])):
+            say("    plan of level %2d: %9d rows, %10d entries, %7d tiles (%d wide): host %8.3f ms (copies %8.3f + plan %8.3f), device %8.3f ms = %.3f%s" % (
+                k, g["rows"], g["stored_entries"], g["tiles"], g["wide_tiles"], g["host_ms"], g["ms"]["host_copy"], g["ms"]["host_plan"], g["ms"]["device"],
+                g["device_over_host"], "; device stages, with a wait between them: " + ", ".join("%s %.3f" % kv for kv in g["device_stage_ms"].items())
+                if "device_stage_ms" in g else ""))
+        dp = res.get("device_plans")
+        if dp and "pcg" in dp:
+            say("    the same cycle over plans made on the device: its plans, smoothers and tables %.4f s (%.4f s with the host's plans)" % (
+                dp["cycle_setup_seconds"], res["cycle_setup_seconds"]))
+            setup = res["hierarchy_seconds"] + dp["cycle_setup_seconds"]
+            for way, g in dp["pcg"].items():
+                say("        pcg device plans %-18s %6d iterations, %8.4f s, with the set-up %8.4f s, r'r / r0'r0 %.3e%s" % (
+                    way, g["iterations"], g["seconds"], g["seconds"] + setup, g["relative_rr"], "" if g["reached"] else " (not reached)"))
         if "pcg" in res:
             say("    the cycle's levels %s, the coarsest by %s; its plans, smoothers and tables: %.4f s" % (
                 " -> ".join(str(n) for n in res["cycle_levels"]), res["coarsest"], res["cycle_setup_seconds"]))
